@@ -18,6 +18,17 @@ local TCP backends.
 
 Scenario configs (BASELINE.json "configs"): headline (default),
 static1, dns, cset, codel, agent — select with --config.
+
+A plain run does only what its result line needs: set up, warm up,
+time the steps, print.  --full is where anything beyond that belongs
+(extra baselines, sweeps, comparisons); today there is nothing of that
+kind in this file, so --full runs the same measurement.
+
+--dump-outputs DIR writes what the callers of the last timed step
+received as DIR/<name>.npy (see dump_outputs below).  The workload has
+no random inputs: every claim is issued with the same empty options,
+so two builds run with the same arguments are comparable output for
+output.
 """
 
 import argparse
@@ -108,11 +119,14 @@ class ClaimDriver:
         self.done_fut = None
         self.active = 0
         self.record_lat = True
+        self.failed = []
 
     def run_step(self, n_ops):
         """Returns a future resolved when n_ops claims completed."""
         self.target = n_ops
         self.ops = 0
+        # completion indices of this step's claims that got an error
+        self.failed = []
         self.done_fut = self.loop.create_future()
         for _ in range(self.concurrency):
             self.active += 1
@@ -125,7 +139,7 @@ class ClaimDriver:
         def cb(err, hdl=None, conn=None):
             if err is not None:
                 # overload shed / timeout: count as completed op
-                pass
+                self.failed.append(self.ops)
             else:
                 hdl.release()
             if self.record_lat:
@@ -139,6 +153,14 @@ class ClaimDriver:
                     self.done_fut.set_result(None)
 
         self.pool.claim({}, cb)
+
+    def last_step_outputs(self):
+        """What the claimers of the last step received, in completion
+        order: 1.0 for a handle + connection, 0.0 for an error."""
+        ok = [1.0] * self.ops
+        for i in self.failed:
+            ok[i] = 0.0
+        return {"claim_ok": ok, "ops_completed": [float(self.ops)]}
 
 
 # ---------------------------------------------------------------------------
@@ -170,6 +192,7 @@ async def scenario_headline(args, results):
 
     results["elapsed"] = t1 - t0
     results["ops"] = args.steps * args.claims_per_step
+    results["outputs"] = driver.last_step_outputs()
     results["lat_p50"] = statistics.median(lat) * 1000 if lat else None
     results["lat_p99"] = (statistics.quantiles(lat, n=100)[98] * 1000
                           if len(lat) >= 100 else None)
@@ -196,6 +219,7 @@ async def scenario_static1(args, results):
     t1 = time.perf_counter()
     results["elapsed"] = t1 - t0
     results["ops"] = args.steps * args.claims_per_step
+    results["outputs"] = driver.last_step_outputs()
     results["lat_p50"] = statistics.median(lat) * 1000 if lat else None
     results["lat_p99"] = (statistics.quantiles(lat, n=100)[98] * 1000
                           if len(lat) >= 100 else None)
@@ -254,6 +278,7 @@ async def scenario_dns(args, results):
     t1 = time.perf_counter()
     results["elapsed"] = t1 - t0
     results["ops"] = args.steps * args.claims_per_step
+    results["outputs"] = driver.last_step_outputs()
     results["lat_p50"] = statistics.median(lat) * 1000 if lat else None
     results["lat_p99"] = (statistics.quantiles(lat, n=100)[98] * 1000
                           if len(lat) >= 100 else None)
@@ -339,6 +364,7 @@ async def scenario_cset(args, results):
     churn_task.cancel()
     results["elapsed"] = t1 - t0
     results["ops"] = ops["n"]
+    results["outputs"] = {"ops_completed": [float(ops["n"])]}
     results["lat_p50"] = None
     results["lat_p99"] = None
     cset.stop()
@@ -358,14 +384,16 @@ async def scenario_codel(args, results):
 
     n = args.claims_per_step
     outcomes = {"ok": 0, "shed": 0}
+    claim_ok = [0.0] * n  # in submission order
     lat = []
     done = loop.create_future()
 
-    def make_cb(t0):
+    def make_cb(t0, i):
         def cb(err, hdl=None, conn=None):
             lat.append(loop.time() - t0)
             if err is None:
                 outcomes["ok"] += 1
+                claim_ok[i] = 1.0
                 # hold briefly to force queueing
                 loop.call_later(0.0005, hdl.release)
             else:
@@ -375,12 +403,15 @@ async def scenario_codel(args, results):
         return cb
 
     t0 = time.perf_counter()
-    for _ in range(n):
-        pool.claim({}, make_cb(loop.time()))
+    for i in range(n):
+        pool.claim({}, make_cb(loop.time(), i))
     await done
     t1 = time.perf_counter()
     results["elapsed"] = t1 - t0
     results["ops"] = n
+    results["steps"] = 1  # one burst, whatever --steps says
+    results["outputs"] = {"claim_ok": claim_ok,
+                          "ops_completed": [float(n)]}
     results["lat_p50"] = statistics.median(lat) * 1000 if lat else None
     results["lat_p99"] = (statistics.quantiles(lat, n=100)[98] * 1000
                           if len(lat) >= 100 else None)
@@ -466,21 +497,26 @@ async def scenario_agent(args, results):
         resp = await agent.request_async("svc.bench", "GET", "/%d" % i)
         lat.append(loop.time() - t0)
         assert resp.status_code == 200
+        return float(resp.status_code)
 
     async def step():
-        await asyncio.gather(*[one_get(i) for i in range(concurrent)])
+        return await asyncio.gather(
+            *[one_get(i) for i in range(concurrent)])
 
     for _ in range(args.warmup):
         await step()
     lat.clear()
+    statuses = []
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        await step()
+        statuses = await step()
     t1 = time.perf_counter()
     barrier()
     results["elapsed"] = t1 - t0
     results["ops"] = args.steps * concurrent
+    results["outputs"] = {"status_code": statuses,
+                          "ops_completed": [float(len(statuses))]}
     results["lat_p50"] = statistics.median(lat) * 1000 if lat else None
     results["lat_p99"] = (statistics.quantiles(lat, n=100)[98] * 1000
                           if len(lat) >= 100 else None)
@@ -576,6 +612,27 @@ def _vs_baseline(config, world, value):
     return round(value / ref, 3)
 
 
+_DUMP_LIMIT_BYTES = 60 * 1000 * 1000  # headers included, under 64 MB
+
+
+def dump_outputs(outputs, dirname):
+    """Write each output of the last timed step as <dirname>/<name>.npy
+    (float32).  The whole dump stays under 64 MB: an array over its
+    share of that is cut down to a fixed, seeded sample of its elements
+    (kept in their original order)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    share = _DUMP_LIMIT_BYTES // max(len(outputs), 1) // 4
+    for name, values in sorted(outputs.items()):
+        arr = np.asarray(values, dtype=np.float32)
+        if arr.size > share:
+            rng = np.random.default_rng(0)
+            idx = np.sort(rng.choice(arr.size, size=share, replace=False))
+            arr = arr[idx]
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
@@ -592,24 +649,36 @@ def main():
     ap.add_argument("--agent-concurrency", type=int, default=1000,
                     help="concurrent GETs in the agent scenario "
                          "(BASELINE config #3 says 1000)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures "
+                         "beyond the result line (nothing so far)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, world = dist_init()
 
     results = {}
     asyncio.run(SCENARIOS[args.config](args, results))
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(results["outputs"], args.dump_outputs)
+
     agg = reduce_results(results, rank, world)
 
     if rank == 0:
         value = agg["ops"] / agg["elapsed"]
-        ms_per_step = (agg["elapsed"] / args.steps) * 1000.0
+        steps = agg.get("steps", args.steps)
+        ms_per_step = (agg["elapsed"] / steps) * 1000.0
         out = {
             "metric": "pool claims/sec (8-backend synthetic TCP set)",
             "value": round(value, 1),
             "unit": "claims/s",
             "n_gpus": world,
-            "steps": args.steps,
+            "steps": steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True,
