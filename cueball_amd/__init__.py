@@ -18,6 +18,7 @@ from .errors import (ClaimHandleMisusedError, ClaimTimeoutError,
 from .events import EventEmitter
 from .fsm import FSM, FSMError
 from .kang import KangServer
+from .latency import LatencyHistogram
 from .metrics import Collector, create_collector
 from .pool import ConnectionPool
 from .pool_monitor import monitor as pool_monitor
@@ -65,6 +66,7 @@ __all__ = [
     "tcp_constructor",
     "KangServer",
     "Collector",
+    "LatencyHistogram",
     "create_collector",
     "HttpAgent",
     "HttpsAgent",

@@ -22,6 +22,9 @@
 #include <Python.h>
 #include <structmember.h>
 #include <cmath>
+#include <ctime>
+
+#include "lathist.h"
 
 namespace {
 
@@ -1692,6 +1695,375 @@ PyTypeObject FSMType = {
 
 
 /* ------------------------------------------------------------------ */
+/* LatencyHistogram / PoolLatency: per-pool claim latency recording.   */
+/* The arithmetic lives in lathist.h (no Python.h, so it is also       */
+/* checked stand-alone); these are the Python faces.  The claim handle */
+/* records into a PoolLatency straight from its state entries: one     */
+/* clock read and one bucket increment, no allocation.                 */
+
+typedef struct {
+    PyObject_HEAD
+    lathist::Hist h;
+} LatHistOb;
+
+extern PyTypeObject LatHistType;
+
+static PyObject *
+LatHist_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
+{
+    (void)args; (void)kwds;
+    LatHistOb *self = (LatHistOb *)type->tp_alloc(type, 0);
+    if (self != NULL)
+        self->h.reset();
+    return (PyObject *)self;
+}
+
+static PyObject *
+LatHist_record(PyObject *self_, PyObject *ms_)
+{
+    double ms = PyFloat_AsDouble(ms_);
+    if (ms == -1.0 && PyErr_Occurred())
+        return NULL;
+    ((LatHistOb *)self_)->h.record_ms(ms);
+    Py_RETURN_NONE;
+}
+
+static PyObject *
+LatHist_counts(PyObject *self_, PyObject *noargs)
+{
+    (void)noargs;
+    const lathist::Hist &h = ((LatHistOb *)self_)->h;
+    PyObject *ls = PyList_New(lathist::NBUCKETS);
+    if (ls == NULL)
+        return NULL;
+    for (int i = 0; i < lathist::NBUCKETS; i++) {
+        PyObject *v = PyLong_FromUnsignedLongLong(h.counts[i]);
+        if (v == NULL) {
+            Py_DECREF(ls);
+            return NULL;
+        }
+        PyList_SET_ITEM(ls, i, v);
+    }
+    return ls;
+}
+
+static PyObject *
+lathist_percentile(const lathist::Hist &h, double q)
+{
+    if (h.count == 0)
+        Py_RETURN_NONE;
+    return PyFloat_FromDouble((double)h.percentile_us(q) / 1000.0);
+}
+
+static PyObject *
+LatHist_percentile(PyObject *self_, PyObject *q_)
+{
+    double q = PyFloat_AsDouble(q_);
+    if (q == -1.0 && PyErr_Occurred())
+        return NULL;
+    return lathist_percentile(((LatHistOb *)self_)->h, q);
+}
+
+/* cumulative(bounds_us) -> [samples with rounded us < bound, ...];
+ * every bound must be a bucket boundary for the counts to be exact */
+static PyObject *
+LatHist_cumulative(PyObject *self_, PyObject *bounds)
+{
+    const lathist::Hist &h = ((LatHistOb *)self_)->h;
+    PyObject *seq = PySequence_Fast(bounds, "bounds must be a sequence");
+    if (seq == NULL)
+        return NULL;
+    Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
+    PyObject *out = PyList_New(n);
+    if (out == NULL) {
+        Py_DECREF(seq);
+        return NULL;
+    }
+    for (Py_ssize_t i = 0; i < n; i++) {
+        unsigned long long b = PyLong_AsUnsignedLongLong(
+            PySequence_Fast_GET_ITEM(seq, i));
+        if (b == (unsigned long long)-1 && PyErr_Occurred()) {
+            Py_DECREF(seq);
+            Py_DECREF(out);
+            return NULL;
+        }
+        PyObject *v = PyLong_FromUnsignedLongLong(
+            h.cumulative_below(lathist::index_us(b)));
+        if (v == NULL) {
+            Py_DECREF(seq);
+            Py_DECREF(out);
+            return NULL;
+        }
+        PyList_SET_ITEM(out, i, v);
+    }
+    Py_DECREF(seq);
+    return out;
+}
+
+static PyObject *
+LatHist_merge(PyObject *self_, PyObject *other)
+{
+    if (!PyObject_TypeCheck(other, &LatHistType)) {
+        PyErr_SetString(PyExc_TypeError,
+                        "merge() needs a native LatencyHistogram");
+        return NULL;
+    }
+    ((LatHistOb *)self_)->h.merge(((LatHistOb *)other)->h);
+    Py_RETURN_NONE;
+}
+
+static PyObject *
+LatHist_reset(PyObject *self_, PyObject *noargs)
+{
+    (void)noargs;
+    ((LatHistOb *)self_)->h.reset();
+    Py_RETURN_NONE;
+}
+
+static PyObject *
+lathist_ms_or_none(const lathist::Hist &h, uint64_t us)
+{
+    if (h.count == 0)
+        Py_RETURN_NONE;
+    return PyFloat_FromDouble((double)us / 1000.0);
+}
+
+static int
+lathist_dict_put(PyObject *d, const char *key, PyObject *v)
+{
+    if (v == NULL)
+        return -1;
+    int r = PyDict_SetItemString(d, key, v);
+    Py_DECREF(v);
+    return r;
+}
+
+static PyObject *
+LatHist_snapshot(PyObject *self_, PyObject *noargs)
+{
+    (void)noargs;
+    const lathist::Hist &h = ((LatHistOb *)self_)->h;
+    PyObject *d = PyDict_New();
+    if (d == NULL)
+        return NULL;
+    if (lathist_dict_put(d, "count",
+                         PyLong_FromUnsignedLongLong(h.count)) < 0 ||
+        lathist_dict_put(d, "sumMs",
+                         PyFloat_FromDouble((double)h.sum_us / 1000.0)) < 0 ||
+        lathist_dict_put(d, "minMs", lathist_ms_or_none(h, h.min_us)) < 0 ||
+        lathist_dict_put(d, "maxMs", lathist_ms_or_none(h, h.max_us)) < 0 ||
+        lathist_dict_put(d, "p50", lathist_percentile(h, 0.5)) < 0 ||
+        lathist_dict_put(d, "p90", lathist_percentile(h, 0.9)) < 0 ||
+        lathist_dict_put(d, "p99", lathist_percentile(h, 0.99)) < 0 ||
+        lathist_dict_put(d, "p999", lathist_percentile(h, 0.999)) < 0) {
+        Py_DECREF(d);
+        return NULL;
+    }
+    return d;
+}
+
+static PyObject *
+LatHist_get_count(PyObject *self_, void *closure)
+{
+    (void)closure;
+    return PyLong_FromUnsignedLongLong(((LatHistOb *)self_)->h.count);
+}
+
+static PyObject *
+LatHist_get_sum_us(PyObject *self_, void *closure)
+{
+    (void)closure;
+    return PyLong_FromUnsignedLongLong(((LatHistOb *)self_)->h.sum_us);
+}
+
+static PyObject *
+LatHist_get_sum_ms(PyObject *self_, void *closure)
+{
+    (void)closure;
+    return PyFloat_FromDouble(
+        (double)((LatHistOb *)self_)->h.sum_us / 1000.0);
+}
+
+static PyObject *
+LatHist_get_min_ms(PyObject *self_, void *closure)
+{
+    (void)closure;
+    const lathist::Hist &h = ((LatHistOb *)self_)->h;
+    return lathist_ms_or_none(h, h.min_us);
+}
+
+static PyObject *
+LatHist_get_max_ms(PyObject *self_, void *closure)
+{
+    (void)closure;
+    const lathist::Hist &h = ((LatHistOb *)self_)->h;
+    return lathist_ms_or_none(h, h.max_us);
+}
+
+static PyMethodDef LatHist_methods[] = {
+    {"record", LatHist_record, METH_O, NULL},
+    {"counts", LatHist_counts, METH_NOARGS, NULL},
+    {"percentile", LatHist_percentile, METH_O, NULL},
+    {"cumulative", LatHist_cumulative, METH_O, NULL},
+    {"merge", LatHist_merge, METH_O, NULL},
+    {"reset", LatHist_reset, METH_NOARGS, NULL},
+    {"snapshot", LatHist_snapshot, METH_NOARGS, NULL},
+    {NULL, NULL, 0, NULL},
+};
+
+static PyGetSetDef LatHist_getset[] = {
+    {(char *)"count", LatHist_get_count, NULL, NULL, NULL},
+    {(char *)"sum_us", LatHist_get_sum_us, NULL, NULL, NULL},
+    {(char *)"sum_ms", LatHist_get_sum_ms, NULL, NULL, NULL},
+    {(char *)"min_ms", LatHist_get_min_ms, NULL, NULL, NULL},
+    {(char *)"max_ms", LatHist_get_max_ms, NULL, NULL, NULL},
+    {NULL, NULL, NULL, NULL, NULL},
+};
+
+PyTypeObject LatHistType = {
+    PyVarObject_HEAD_INIT(NULL, 0)
+    "cueball_amd._speed.LatencyHistogram",
+    sizeof(LatHistOb),
+};
+
+/* PoolLatency(loop, direct): the pool's wait/hold/connect histograms
+ * and the clock the claim handle reads.  direct != 0 (decided once per
+ * pool, only for the stock asyncio loop clock) reads CLOCK_MONOTONIC
+ * in C -- the same clock time.monotonic() reads; any other loop is
+ * asked through loop.time(). */
+typedef struct {
+    PyObject_HEAD
+    PyObject *pl_loop;
+    LatHistOb *pl_wait;
+    LatHistOb *pl_hold;
+    LatHistOb *pl_connect;
+    int pl_direct;
+} PoolLatOb;
+
+extern PyTypeObject PoolLatType;
+PyObject *s_p_lat;               /* "p_lat" */
+extern PyObject *s_time;         /* "time" (ClaimHandleBase section) */
+
+/* the pool clock in ms; *err set on a python failure */
+static inline double
+poollat_now_ms(PoolLatOb *pl, int *err)
+{
+#if defined(CLOCK_MONOTONIC)
+    if (pl->pl_direct) {
+        struct timespec ts;
+        if (clock_gettime(CLOCK_MONOTONIC, &ts) == 0)
+            return (double)ts.tv_sec * 1000.0 + (double)ts.tv_nsec * 1e-6;
+    }
+#endif
+    PyObject *t = PyObject_CallMethodObjArgs(pl->pl_loop, s_time, NULL);
+    if (t == NULL) {
+        *err = 1;
+        return 0.0;
+    }
+    double secs = PyFloat_AsDouble(t);
+    Py_DECREF(t);
+    if (secs == -1.0 && PyErr_Occurred()) {
+        *err = 1;
+        return 0.0;
+    }
+    return secs * 1000.0;
+}
+
+static PyObject *
+PoolLat_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
+{
+    PyObject *loop;
+    int direct = 0;
+    static const char *kwlist[] = {"loop", "direct", NULL};
+    if (!PyArg_ParseTupleAndKeywords(args, kwds, "O|p",
+                                     const_cast<char **>(kwlist),
+                                     &loop, &direct))
+        return NULL;
+    PoolLatOb *self = PyObject_GC_New(PoolLatOb, type);
+    if (self == NULL)
+        return NULL;
+    Py_INCREF(loop);
+    self->pl_loop = loop;
+#if defined(CLOCK_MONOTONIC)
+    self->pl_direct = direct;
+#else
+    self->pl_direct = 0;
+#endif
+    self->pl_wait = (LatHistOb *)LatHist_new(&LatHistType, NULL, NULL);
+    self->pl_hold = (LatHistOb *)LatHist_new(&LatHistType, NULL, NULL);
+    self->pl_connect = (LatHistOb *)LatHist_new(&LatHistType, NULL, NULL);
+    PyObject_GC_Track((PyObject *)self);
+    if (self->pl_wait == NULL || self->pl_hold == NULL ||
+        self->pl_connect == NULL) {
+        Py_DECREF((PyObject *)self);
+        return NULL;
+    }
+    return (PyObject *)self;
+}
+
+static int
+PoolLat_traverse(PyObject *self_, visitproc visit, void *arg)
+{
+    Py_VISIT(((PoolLatOb *)self_)->pl_loop);
+    return 0;
+}
+
+static int
+PoolLat_clear_(PyObject *self_)
+{
+    Py_CLEAR(((PoolLatOb *)self_)->pl_loop);
+    return 0;
+}
+
+static void
+PoolLat_dealloc(PyObject *self_)
+{
+    PoolLatOb *self = (PoolLatOb *)self_;
+    PyObject_GC_UnTrack(self_);
+    Py_CLEAR(self->pl_loop);
+    Py_CLEAR(self->pl_wait);
+    Py_CLEAR(self->pl_hold);
+    Py_CLEAR(self->pl_connect);
+    PyObject_GC_Del(self_);
+}
+
+static PyMemberDef PoolLat_members[] = {
+    {(char *)"loop", T_OBJECT, offsetof(PoolLatOb, pl_loop), READONLY,
+     NULL},
+    {(char *)"wait", T_OBJECT, offsetof(PoolLatOb, pl_wait), READONLY,
+     NULL},
+    {(char *)"hold", T_OBJECT, offsetof(PoolLatOb, pl_hold), READONLY,
+     NULL},
+    {(char *)"connect", T_OBJECT, offsetof(PoolLatOb, pl_connect),
+     READONLY, NULL},
+    {(char *)"direct", T_INT, offsetof(PoolLatOb, pl_direct), READONLY,
+     NULL},
+    {NULL, 0, 0, 0, NULL},
+};
+
+PyTypeObject PoolLatType = {
+    PyVarObject_HEAD_INIT(NULL, 0)
+    "cueball_amd._speed.PoolLatency",
+    sizeof(PoolLatOb),
+};
+
+static void
+latency_types_init(void)
+{
+    LatHistType.tp_flags = Py_TPFLAGS_DEFAULT;
+    LatHistType.tp_methods = LatHist_methods;
+    LatHistType.tp_getset = LatHist_getset;
+    LatHistType.tp_new = LatHist_new;
+
+    PoolLatType.tp_dealloc = PoolLat_dealloc;
+    PoolLatType.tp_flags = Py_TPFLAGS_DEFAULT | Py_TPFLAGS_HAVE_GC;
+    PoolLatType.tp_traverse = PoolLat_traverse;
+    PoolLatType.tp_clear = PoolLat_clear_;
+    PoolLatType.tp_members = PoolLat_members;
+    PoolLatType.tp_new = PoolLat_new;
+}
+
+/* ------------------------------------------------------------------ */
 /* ClaimHandleBase: the pool claim handle's hot path in C              */
 /* ------------------------------------------------------------------ */
 
@@ -1728,14 +2100,17 @@ typedef struct {
     PyObject *chb_release_stack;
     PyObject *chb_connection;
     PyObject *chb_last_error;
+    PoolLatOb *chb_lat;     /* the pool's latency recorder, or NULL */
     double chb_claim_timeout;
     double chb_started;
+    double chb_claimed_at;  /* valid while chb_lat_open */
     long chb_pre[4];
     int chb_have_pre;
     int chb_throw_error;
     int chb_cancelled;
     int chb_leak_check;
     int chb_pinger;
+    int chb_lat_open;       /* wait recorded, hold still running */
 } CHOb;
 
 extern PyTypeObject CHType;
@@ -2264,12 +2639,40 @@ CH_state_claimed(PyObject *self_, PyObject *scope)
         return NULL;
     Py_DECREF(r);
 
+    /* the wait ends here, just before the user callback; pinger
+     * claims are the pool's own and not counted */
+    if (self->chb_lat != NULL && !self->chb_pinger) {
+        int err = 0;
+        double now = poollat_now_ms(self->chb_lat, &err);
+        if (err)
+            return NULL;
+        self->chb_lat->pl_wait->h.record_ms(now - self->chb_started);
+        self->chb_claimed_at = now;
+        self->chb_lat_open = 1;
+    }
+
     PyObject *cbargs[3] = {Py_None, self_, conn};
     r = PyObject_Vectorcall(self->chb_callback, cbargs, 3, NULL);
     if (r == NULL)
         return NULL;
     Py_DECREF(r);
     Py_RETURN_NONE;
+}
+
+/* claimed -> released/closed: the lease ends.  Only a handle whose
+ * wait was recorded (reached its callback, not a pinger) has a hold */
+static int
+ch_record_hold(CHOb *self)
+{
+    if (!self->chb_lat_open)
+        return 0;
+    self->chb_lat_open = 0;
+    int err = 0;
+    double now = poollat_now_ms(self->chb_lat, &err);
+    if (err)
+        return -1;
+    self->chb_lat->pl_hold->h.record_ms(now - self->chb_claimed_at);
+    return 0;
 }
 
 PyObject *
@@ -2279,6 +2682,8 @@ CH_state_released(PyObject *self_, PyObject *scope)
     (void)scope;
     Py_INCREF(t_empty);
     Py_XSETREF(self->base.f_valid, t_empty);
+    if (ch_record_hold(self) < 0)
+        return NULL;
     if (!self->chb_leak_check || !self->chb_have_pre)
         Py_RETURN_NONE;
     PyObject *conn = self->chb_connection;
@@ -2311,6 +2716,8 @@ CH_state_closed(PyObject *self_, PyObject *scope)
     (void)scope;
     Py_INCREF(t_empty);
     Py_XSETREF(self->base.f_valid, t_empty);
+    if (ch_record_hold(self) < 0)
+        return NULL;
     Py_RETURN_NONE;
 }
 
@@ -2412,6 +2819,7 @@ CH_traverse(PyObject *self_, visitproc visit, void *arg)
     Py_VISIT(self->chb_release_stack);
     Py_VISIT(self->chb_connection);
     Py_VISIT(self->chb_last_error);
+    Py_VISIT((PyObject *)self->chb_lat);
     return FSM_traverse(self_, visit, arg);
 }
 
@@ -2427,6 +2835,7 @@ CH_clear_(PyObject *self_)
     Py_CLEAR(self->chb_release_stack);
     Py_CLEAR(self->chb_connection);
     Py_CLEAR(self->chb_last_error);
+    Py_CLEAR(self->chb_lat);
     return FSM_clear_(self_);
 }
 
@@ -2468,6 +2877,14 @@ CH__setup(PyObject *self_, PyObject *const *args, Py_ssize_t nargs)
     self->chb_leak_check = 1;
     self->chb_pinger = 0;
     self->chb_have_pre = 0;
+    self->chb_lat_open = 0;
+    /* the pool's latency recorder, if it keeps one (latencyStats) */
+    PyObject *lat = NULL;
+    if (_PyObject_LookupAttr(args[0], s_p_lat, &lat) < 0)
+        return NULL;
+    if (lat != NULL && Py_TYPE(lat) != &PoolLatType)
+        Py_CLEAR(lat);
+    Py_XSETREF(self->chb_lat, (PoolLatOb *)lat);
 
     /* FSM init (resolves loop, enters "waiting") */
     PyObject *resolved = PyObject_CallOneArg(g_get_loop, args[6]);
@@ -2488,6 +2905,15 @@ CH__setup(PyObject *self_, PyObject *const *args, Py_ssize_t nargs)
     }
     if (fsm_goto_state(&self->base, s_waiting) < 0)
         return NULL;
+    if (self->chb_lat != NULL && self->chb_lat->pl_direct &&
+        self->chb_lat->pl_loop == self->base.f_loop) {
+        /* stock loop clock: same reading without the python call */
+        int err = 0;
+        self->chb_started = poollat_now_ms(self->chb_lat, &err);
+        if (err)
+            return NULL;
+        Py_RETURN_NONE;
+    }
     PyObject *t = PyObject_CallMethodObjArgs(self->base.f_loop, s_time,
                                              NULL);
     if (t == NULL)
@@ -4807,6 +5233,11 @@ PyInit__speed(void)
     ct_type_init();
     slotkit_types_init();
     codel_type_init();
+    s_p_lat = PyUnicode_InternFromString("p_lat");
+    latency_types_init();
+    if (PyType_Ready(&LatHistType) < 0 ||
+        PyType_Ready(&PoolLatType) < 0)
+        return NULL;
     if (PyType_Ready(&EmitterType) < 0 ||
         PyType_Ready(&OnceWrapperType) < 0 ||
         PyType_Ready(&GuardedCbType) < 0 ||
@@ -4855,5 +5286,9 @@ PyInit__speed(void)
     PyModule_AddObject(m, "SlotDispatch", (PyObject *)&SlotDispatchType);
     Py_INCREF(&CoDelType);
     PyModule_AddObject(m, "ControlledDelay", (PyObject *)&CoDelType);
+    Py_INCREF(&LatHistType);
+    PyModule_AddObject(m, "LatencyHistogram", (PyObject *)&LatHistType);
+    Py_INCREF(&PoolLatType);
+    PyModule_AddObject(m, "PoolLatency", (PyObject *)&PoolLatType);
     return m;
 }

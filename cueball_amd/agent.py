@@ -96,6 +96,7 @@ class Agent(EventEmitter):
         self.cba_recovery = recovery
 
         self.cba_err_on_empty = bool(options.get("errorOnEmpty"))
+        self.cba_latency_stats = options.get("latencyStats")
 
         for host in options.get("initialDomains") or ():
             self._add_pool(host, {})
@@ -191,6 +192,8 @@ class Agent(EventEmitter):
             "collector": self.collector,
             "loop": self._loop,
         }
+        if self.cba_latency_stats is not None:
+            pool_opts["latencyStats"] = self.cba_latency_stats
         if self.cba_ping is not None:
             pool_opts["checkTimeout"] = self.cba_ping_interval or 30000
             pool_opts["checker"] = \
@@ -206,6 +209,11 @@ class Agent(EventEmitter):
 
     def get_pool(self, host: str) -> Optional[ConnectionPool]:
         return self.pools.get(host)
+
+    def get_latency_stats(self) -> Dict[str, Any]:
+        """Per-host ``ConnectionPool.get_latency_stats()``."""
+        return {host: pool.get_latency_stats()
+                for host, pool in self.pools.items()}
 
     def create_pool(self, host: str,
                     options: Optional[Dict[str, Any]] = None) -> None:

@@ -187,6 +187,11 @@ class SocketMgrFSM(FSM):
 
     def state_connecting(self, S: StateScope) -> None:
         S.valid_transitions(["connected", "error"])
+        # connect latency: this entry -> the socket's 'connect' event,
+        # successful connects only (a pool without latencyStats, or a
+        # ConnectionSet, has no p_lat)
+        lat = getattr(self.sm_pool, "p_lat", None)
+        started = self._loop.time() if lat is not None else 0.0
 
         def on_timeout() -> None:
             self.sm_last_error = mod_errors.ConnectionTimeoutError(
@@ -203,7 +208,12 @@ class SocketMgrFSM(FSM):
         self.sm_socket = sock
         sock.sm_fsm = self
 
-        S.on(sock, "connect", lambda: S.goto_state("connected"))
+        def on_connect() -> None:
+            if lat is not None:
+                lat.connect.record((self._loop.time() - started) * 1000.0)
+            S.goto_state("connected")
+
+        S.on(sock, "connect", on_connect)
 
         def on_error(err: BaseException) -> None:
             self.sm_last_error = mod_errors.ConnectionError_(
@@ -326,6 +336,8 @@ class ClaimHandle(FSM):
     ch_do_release_leak_check = True
     ch_pinger = False
     ch_pre_listeners: Any = None
+    #: claim time of a handle whose wait was recorded (None otherwise)
+    ch_claimed_at: Optional[float] = None
 
     def __init__(self, options: Dict[str, Any]) -> None:
         self.ch_claim_timeout = options["claimTimeout"]
@@ -338,6 +350,8 @@ class ClaimHandle(FSM):
         # hot path: the pool passes a pre-made child logger
         self.ch_log = log if options.get("_logReady") \
             else log.child(component="ClaimHandle")
+
+        self.ch_lat = getattr(self.ch_pool, "p_lat", None)
 
         super().__init__("waiting", loop=options.get("loop"))
         self.ch_started = self._loop.time() * 1000.0
@@ -355,6 +369,7 @@ class ClaimHandle(FSM):
         self.ch_claim_stack = claim_stack
         self.ch_callback = callback
         self.ch_log = log
+        self.ch_lat = getattr(pool, "p_lat", None)
         FSM.__init__(self, "waiting", loop=loop)
         self.ch_started = self._loop.time() * 1000.0
         return self
@@ -499,10 +514,26 @@ class ClaimHandle(FSM):
         self.ch_pre_listeners = (cnt(conn, "close"), cnt(conn, "error"),
                                  cnt(conn, "readable"), cnt(conn, "data"))
         S.on(conn, "error", self._on_claimed_conn_error)
+        # the wait ends here, just before the user callback; pinger
+        # claims are the pool's own and not counted
+        lat = self.ch_lat
+        if lat is not None and not self.ch_pinger:
+            now = self._loop.time() * 1000.0
+            lat.wait.record(now - self.ch_started)
+            self.ch_claimed_at = now
         self.ch_callback(None, self, conn)
+
+    def _record_hold(self) -> None:
+        """claimed -> released/closed: the lease ends.  Only a handle
+        whose wait was recorded has a hold."""
+        at = self.ch_claimed_at
+        if at is not None:
+            self.ch_claimed_at = None
+            self.ch_lat.hold.record(self._loop.time() * 1000.0 - at)
 
     def state_released(self, S: StateScope) -> None:
         S.valid_transitions([])
+        self._record_hold()
         if not self.ch_do_release_leak_check:
             return
         conn = self.ch_connection
@@ -520,6 +551,7 @@ class ClaimHandle(FSM):
 
     def state_closed(self, S: StateScope) -> None:
         S.valid_transitions([])
+        self._record_hold()
         # no leak check: the connection is being torn down anyway
 
     def state_cancelled(self, S: StateScope) -> None:

@@ -25,10 +25,11 @@ from typing import Any, Callable, Dict, List, Optional
 
 from . import codel as mod_codel
 from . import errors as mod_errors
+from . import latency as mod_latency
 from . import utils as mod_utils
 from .connection_fsm import ClaimHandle, ConnectionSlotFSM
 from .events import EventEmitter
-from .fsm import FSM, StateScope
+from .fsm import FSM, StateScope, get_loop
 from .logutil import CueballLogger, default_logger
 from .pool_monitor import monitor as global_monitor
 from .queue import Queue
@@ -260,6 +261,21 @@ class ConnectionPool(FSM):
         if tcd is not None and math.isfinite(tcd):
             self.p_codel = mod_codel.ControlledDelay(tcd, loop=loop_opt)
 
+        # Latency histograms (claim wait, claim hold, connect).  The
+        # claim handle records into p_lat directly from its state
+        # entries; the collector only ever sees a snapshot, published
+        # from _lp_tick.
+        latency_stats = options.get("latencyStats")
+        if latency_stats is None:
+            latency_stats = True
+        if not isinstance(latency_stats, bool):
+            raise TypeError("options.latencyStats must be a bool")
+        self.p_lat = None
+        self._lat_metrics: List[tuple] = []
+        if latency_stats:
+            self.p_lat = mod_latency.PoolLatency(get_loop(loop_opt))
+            self._register_latency_metrics()
+
         self.p_last_error: Optional[BaseException] = None
         self.p_counters: Dict[str, int] = {}
 
@@ -325,6 +341,54 @@ class ConnectionPool(FSM):
         if busy + extras > self.p_demand_hwm:
             self.p_demand_hwm = busy + extras
 
+    # -- latency histograms -----------------------------------------------
+    _LAT_METRICS = (
+        ("wait", "cueball_claim_wait_seconds",
+         "Time from claim() to the claim callback, served claims only"),
+        ("hold", "cueball_claim_hold_seconds",
+         "Time a claimed connection was held before release/close"),
+        ("connect", "cueball_connect_seconds",
+         "Time from starting a connect to the connect event"),
+    )
+
+    def _register_latency_metrics(self) -> None:
+        """One Prometheus histogram per pool histogram, with the same
+        labels as cueball_pool_connections.  The ``le`` bounds are
+        4**k us (k = 2..13) in seconds; each is an internal bucket
+        boundary, so the published counts are exact.  Half-open
+        convention: an observation counts under ``le=L`` when its
+        value, rounded to whole microseconds, is < L."""
+        bounds = [us / 1e6 for us in mod_latency.EXPOSITION_BOUNDS_US]
+        try:
+            for attr, name, help_ in self._LAT_METRICS:
+                m = self.p_collector.histogram(name=name, help=help_,
+                                               buckets=bounds)
+                self._lat_metrics.append((getattr(self.p_lat, attr), m))
+        except (AttributeError, ValueError, TypeError):
+            # foreign collector without (compatible) histograms
+            self._lat_metrics = []
+
+    def _publish_latency(self) -> None:
+        labels = self._gauge_labels or {
+            "pool": self.p_uuid.split("-")[0], "domain": self.p_domain}
+        for hist, metric in self._lat_metrics:
+            metric.set_cumulative(
+                hist.cumulative(mod_latency.EXPOSITION_BOUNDS_US),
+                hist.sum_us / 1e6, hist.count, labels)
+
+    def get_latency_stats(self) -> Optional[Dict[str, Any]]:
+        """Snapshots of the pool's latency histograms, times in ms:
+        ``{"claimWait": snap, "claimHold": snap, "connect": snap}`` with
+        ``snap = {"count", "sumMs", "minMs", "maxMs", "p50", "p90",
+        "p99", "p999"}``; None when the pool was created with
+        ``latencyStats: False``."""
+        lat = self.p_lat
+        if lat is None:
+            return None
+        return {"claimWait": lat.wait.snapshot(),
+                "claimHold": lat.hold.snapshot(),
+                "connect": lat.connect.snapshot()}
+
     # -- LPF anti-shrink sampling (lib/pool.js:251-263) ------------------
     def _lp_tick(self) -> None:
         conns = sum(len(v) for v in self.p_connections.values())
@@ -343,6 +407,8 @@ class ConnectionPool(FSM):
             g.set(len(self.p_idleq), {**labels, "state": "idle"})
             g.set(len(self.p_initq), {**labels, "state": "pending"})
             g.set(len(self.p_waiters), {**labels, "state": "waiting"})
+        if self._lat_metrics:
+            self._publish_latency()
         if self.p_last_rebal_clamped:
             self.rebalance()
 

@@ -67,6 +67,14 @@ async def main():
             if shown >= 5:
                 break
 
+    # the same latency data in-process, without a scrape (times in ms)
+    for host, stats in agent.get_latency_stats().items():
+        for which in ("claimWait", "claimHold", "connect"):
+            snap = stats[which]
+            print("latency %s %s: n=%d p50=%s p99=%s max=%s"
+                  % (host, which, snap["count"], snap["p50"], snap["p99"],
+                     snap["maxMs"]))
+
     kang.stop()
     fut = loop.create_future()
     agent.stop(lambda e: fut.set_result(None))

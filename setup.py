@@ -18,6 +18,7 @@ if os.path.exists(os.path.join(ROOT, speed_src)):
     ext_modules.append(Extension(
         "cueball_amd._speed",
         sources=[speed_src],
+        depends=[os.path.join("cueball_amd", "_native", "lathist.h")],
         language="c++",
         extra_compile_args=["-O3", "-std=c++17", "-fvisibility=hidden"],
     ))
