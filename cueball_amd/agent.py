@@ -97,6 +97,11 @@ class Agent(EventEmitter):
 
         self.cba_err_on_empty = bool(options.get("errorOnEmpty"))
         self.cba_latency_stats = options.get("latencyStats")
+        # handed to every pool and DNS resolver this agent creates
+        srv_ranking = options.get("srvRanking")
+        if srv_ranking is not None and not isinstance(srv_ranking, bool):
+            raise TypeError("options.srvRanking must be a bool")
+        self.cba_srv_ranking = bool(srv_ranking)
 
         for host in options.get("initialDomains") or ():
             self._add_pool(host, {})
@@ -116,16 +121,19 @@ class Agent(EventEmitter):
         if use_external:
             res = options["resolver"]
         else:
+            resolver_config = {
+                "resolvers": self.resolvers,
+                "service": self.service,
+                "defaultPort": def_port,
+                "recovery": self.cba_recovery,
+                "log": self.log,
+                "loop": self._loop,
+            }
+            if self.cba_srv_ranking:
+                resolver_config["srvRanking"] = True
             res = resolver_for_ip_or_domain({
                 "input": host,
-                "resolverConfig": {
-                    "resolvers": self.resolvers,
-                    "service": self.service,
-                    "defaultPort": def_port,
-                    "recovery": self.cba_recovery,
-                    "log": self.log,
-                    "loop": self._loop,
-                },
+                "resolverConfig": resolver_config,
             })
             if isinstance(res, Exception):
                 raise res
@@ -194,6 +202,8 @@ class Agent(EventEmitter):
         }
         if self.cba_latency_stats is not None:
             pool_opts["latencyStats"] = self.cba_latency_stats
+        if self.cba_srv_ranking:
+            pool_opts["srvRanking"] = True
         if self.cba_ping is not None:
             pool_opts["checkTimeout"] = self.cba_ping_interval or 30000
             pool_opts["checker"] = \

@@ -12,6 +12,8 @@ Options (DNS lookups):
     -s/--service       SRV "service" name (e.g. _http._tcp)
     -t/--timeout       lookup timeout (e.g. 5000, 5s, 1m)
     -k/--kang-port     start a kang snapshot listener on this port
+    -w/--srv-ranking   honor SRV priority/weight: print both as extra
+                       columns, and report rank changes with -f
 """
 
 from __future__ import annotations
@@ -77,6 +79,8 @@ def main(argv: Optional[list] = None) -> int:
                     help="timeout for lookups (e.g. 5000, 5s, 1m)")
     ap.add_argument("-k", "--kang-port", type=int, default=None,
                     help="start kang listener on this port")
+    ap.add_argument("-w", "--srv-ranking", action="store_true",
+                    help="show SRV priority and weight of each backend")
     ap.add_argument("names", nargs="+", metavar="HOSTNAME[:PORT]")
     args = ap.parse_args(argv)
 
@@ -99,6 +103,8 @@ def main(argv: Optional[list] = None) -> int:
             ip for ip in args.resolvers.split(",") if ip]
     if args.service:
         resolver_conf["service"] = args.service
+    if args.srv_ranking:
+        resolver_conf["srvRanking"] = True
 
     rc = {"code": 0}
 
@@ -143,15 +149,36 @@ def main(argv: Optional[list] = None) -> int:
                 rc["code"] = 2
                 return
 
+        def rank_cols(backend: Dict[str, Any]) -> str:
+            return "%5d %5d" % (backend.get("priority", 0),
+                                backend.get("weight", 0))
+
         def on_added(key: str, backend: Dict[str, Any]) -> None:
             backends[key] = backend
-            if args.follow:
+            if args.follow and args.srv_ranking:
+                print("%s added   %16s:%-5d %s (%s)" % (
+                    time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()),
+                    backend["address"], backend["port"],
+                    rank_cols(backend), key))
+            elif args.follow:
                 print("%s added   %16s:%-5d (%s)" % (
                     time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()),
                     backend["address"], backend["port"], key))
+            elif args.srv_ranking:
+                print("%-16s %5d %s %s" % (backend["address"],
+                                           backend["port"],
+                                           rank_cols(backend), key))
             else:
                 print("%-16s %5d %s" % (backend["address"],
                                         backend["port"], key))
+
+        def on_changed(key: str, backend: Dict[str, Any]) -> None:
+            backends[key] = backend
+            if args.follow:
+                print("%s changed %16s:%-5d %s (%s)" % (
+                    time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()),
+                    backend["address"], backend["port"],
+                    rank_cols(backend), key))
 
         def on_removed(key: str) -> None:
             old = backends.pop(key, None)
@@ -162,6 +189,8 @@ def main(argv: Optional[list] = None) -> int:
 
         resolver.on("added", on_added)
         resolver.on("removed", on_removed)
+        if args.srv_ranking:
+            resolver.on("changed", on_changed)
 
         def on_state(st: str) -> None:
             if args.follow:

@@ -31,6 +31,11 @@ __all__ = ["ConnectionSet", "LogicalConnection"]
 
 
 class ConnectionSet(FSM):
+    # SRV ranking state: class-level defaults, instance attributes only
+    # with srvRanking on (as in ConnectionPool)
+    cs_ranks: Optional[Dict[str, tuple]] = None
+    cs_active_priority: Optional[int] = None
+
     def __init__(self, options: Dict[str, Any]) -> None:
         if not callable(options.get("constructor")):
             raise TypeError("options.constructor (callable) is required")
@@ -84,6 +89,16 @@ class ConnectionSet(FSM):
         self.cs_counters: Dict[str, int] = {}
         self.cs_last_error: Optional[BaseException] = None
 
+        # SRV ranking (opt-in): key -> (priority, weight) for the
+        # rebalance planner; None when off
+        srv_ranking = options.get("srvRanking")
+        if srv_ranking is None:
+            srv_ranking = False
+        if not isinstance(srv_ranking, bool):
+            raise TypeError("options.srvRanking must be a bool")
+        if srv_ranking:
+            self.cs_ranks = {}
+
         super().__init__("starting", loop=loop_opt)
 
         self.cs_rebal_timer = _IntervalTimer(self._loop, 10_000)
@@ -101,7 +116,27 @@ class ConnectionSet(FSM):
         idx = random.randrange(len(self.cs_keys) + 1)
         self.cs_keys.insert(idx, k)
         self.cs_backends[k] = backend
+        if self.cs_ranks is not None:
+            self.cs_ranks[k] = (backend.get("priority", 0),
+                                backend.get("weight", 0))
         self.rebalance()
+
+    def _on_resolver_changed(self, k: str, backend: Dict[str, Any]) -> None:
+        """A known backend's SRV rank changed (srvRanking only)."""
+        if k not in self.cs_backends:
+            return
+        # update in place: a live slot holds a reference to this dict
+        self.cs_backends[k].update(backend)
+        self.cs_backends[k]["key"] = k
+        self.cs_ranks[k] = (backend.get("priority", 0),
+                            backend.get("weight", 0))
+        self.rebalance()
+
+    def _subscribe_resolver(self, S: StateScope) -> None:
+        S.on(self.cs_resolver, "added", self._on_resolver_added)
+        S.on(self.cs_resolver, "removed", self._on_resolver_removed)
+        if self.cs_ranks is not None:
+            S.on(self.cs_resolver, "changed", self._on_resolver_changed)
 
     def _on_resolver_removed(self, k: str) -> None:
         try:
@@ -111,6 +146,8 @@ class ConnectionSet(FSM):
                 "Resolver removed key that is not present in cs_keys")
         self.cs_backends.pop(k, None)
         self.cs_dead.pop(k, None)
+        if self.cs_ranks is not None:
+            self.cs_ranks.pop(k, None)
 
         fsm = self.cs_fsm.get(k)
         if fsm is not None:
@@ -131,8 +168,7 @@ class ConnectionSet(FSM):
         S.valid_transitions(["failed", "running", "stopping"])
         global_monitor.register_set(self)
 
-        S.on(self.cs_resolver, "added", self._on_resolver_added)
-        S.on(self.cs_resolver, "removed", self._on_resolver_removed)
+        self._subscribe_resolver(S)
 
         if self.cs_resolver.is_in_state("failed"):
             self.cs_log.warn('resolver has already failed, cset will start '
@@ -168,8 +204,7 @@ class ConnectionSet(FSM):
 
     def state_failed(self, S: StateScope) -> None:
         S.valid_transitions(["running", "stopping"])
-        S.on(self.cs_resolver, "added", self._on_resolver_added)
-        S.on(self.cs_resolver, "removed", self._on_resolver_removed)
+        self._subscribe_resolver(S)
         S.on(self.cs_shuffle_timer, "timeout", self.reshuffle)
 
         def on_connected(*a: Any) -> None:
@@ -184,8 +219,7 @@ class ConnectionSet(FSM):
 
     def state_running(self, S: StateScope) -> None:
         S.valid_transitions(["failed", "stopping"])
-        S.on(self.cs_resolver, "added", self._on_resolver_added)
-        S.on(self.cs_resolver, "removed", self._on_resolver_removed)
+        self._subscribe_resolver(S)
         S.on(self.cs_rebal_timer, "timeout", self.rebalance)
         S.on(self.cs_shuffle_timer, "timeout", self.reshuffle)
 
@@ -293,6 +327,24 @@ class ConnectionSet(FSM):
             "deadBackends": len(self.cs_dead),
         }
 
+    def get_ranking(self) -> Dict[str, Any]:
+        """SRV ranking as the set sees it; same shape as
+        ``ConnectionPool.get_ranking()``."""
+        return mod_utils.ranking_report(
+            self.cs_keys, self.cs_dead, self.cs_ranks,
+            {k: 1 for k in self.cs_fsm})
+
+    def _note_active_priority(self, new: Optional[int]) -> None:
+        old = self.cs_active_priority
+        if new == old:
+            return
+        self.cs_active_priority = new
+        if old is None or new is None:
+            return  # first backends seen: nothing to fail over from
+        self.cs_log.info("failing %s to priority %d"
+                         % ("over" if new > old else "back", new))
+        self.emit("priorityChanged", old, new)
+
     # -- rebalancing --------------------------------------------------------
     def rebalance(self) -> None:
         if len(self.cs_keys) < 1:
@@ -322,8 +374,13 @@ class ConnectionSet(FSM):
                     working += 1
                 total += 1
 
+        ranks = self.cs_ranks
         plan = mod_utils.plan_rebalance(conns, self.cs_dead, self.cs_target,
-                                        self.cs_max, singleton=True)
+                                        self.cs_max, singleton=True,
+                                        ranks=ranks)
+        if ranks is not None:
+            self._note_active_priority(mod_utils.active_priority(
+                self.cs_keys, self.cs_dead, ranks))
 
         if plan["remove"] or plan["add"]:
             self.cs_log.trace("rebalancing cset, remove %d, add %d "

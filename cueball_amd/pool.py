@@ -166,6 +166,15 @@ class _IntervalTimer(EventEmitter):
 
 
 class ConnectionPool(FSM):
+    # SRV ranking state.  Class-level defaults, so that a pool without
+    # srvRanking carries no extra instance attribute: native code looks
+    # attributes up in the instance dict on every claim, and that dict
+    # stays exactly what it was.
+    p_ranks: Optional[Dict[str, tuple]] = None
+    p_rank_gen = 0
+    p_active_priority: Optional[int] = None
+    _prio_gauge = None
+
     def __init__(self, options: Dict[str, Any]) -> None:
         if not callable(options.get("constructor")):
             raise TypeError("options.constructor (callable) is required")
@@ -279,6 +288,24 @@ class ConnectionPool(FSM):
         self.p_last_error: Optional[BaseException] = None
         self.p_counters: Dict[str, int] = {}
 
+        # SRV ranking (opt-in): key -> (priority, weight), handed to the
+        # rebalance planner; None when off.  p_rank_gen counts rank
+        # edits for the no-op census.
+        srv_ranking = options.get("srvRanking")
+        if srv_ranking is None:
+            srv_ranking = False
+        if not isinstance(srv_ranking, bool):
+            raise TypeError("options.srvRanking must be a bool")
+        if srv_ranking:
+            self.p_ranks = {}
+        if srv_ranking and self._gauge is not None:
+            try:
+                self._prio_gauge = self.p_collector.gauge(
+                    name="cueball_pool_active_priority",
+                    help="SRV priority tier the pool is currently using")
+            except (AttributeError, ValueError):
+                pass
+
         if options.get("resolver") is not None:
             self.p_resolver = options["resolver"]
             self.p_resolver_custom = True
@@ -293,6 +320,7 @@ class ConnectionPool(FSM):
                 "log": self.p_log,
                 "recovery": recovery,
                 "loop": loop_opt,
+                "srvRanking": srv_ranking,
             })
             self.p_resolver_custom = False
 
@@ -409,6 +437,9 @@ class ConnectionPool(FSM):
             g.set(len(self.p_waiters), {**labels, "state": "waiting"})
         if self._lat_metrics:
             self._publish_latency()
+        if self._prio_gauge is not None and \
+                self.p_active_priority is not None:
+            self._prio_gauge.set(self.p_active_priority, self._gauge_labels)
         if self.p_last_rebal_clamped:
             self.rebalance()
 
@@ -418,7 +449,31 @@ class ConnectionPool(FSM):
         idx = random.randrange(len(self.p_keys) + 1)
         self.p_keys.insert(idx, k)
         self.p_backends[k] = backend
+        if self.p_ranks is not None:
+            self.p_ranks[k] = (backend.get("priority", 0),
+                               backend.get("weight", 0))
+            self.p_rank_gen += 1
         self.rebalance()
+
+    def _on_resolver_changed(self, k: str, backend: Dict[str, Any]) -> None:
+        """A known backend's SRV rank changed (srvRanking only): same
+        key, so no connection is touched here; the rebalance moves the
+        spread."""
+        if k not in self.p_backends:
+            return
+        # update in place: live slots hold a reference to this dict
+        self.p_backends[k].update(backend)
+        self.p_backends[k]["key"] = k
+        self.p_ranks[k] = (backend.get("priority", 0),
+                           backend.get("weight", 0))
+        self.p_rank_gen += 1
+        self.rebalance()
+
+    def _subscribe_resolver(self, S: StateScope) -> None:
+        S.on(self.p_resolver, "added", self._on_resolver_added)
+        S.on(self.p_resolver, "removed", self._on_resolver_removed)
+        if self.p_ranks is not None:
+            S.on(self.p_resolver, "changed", self._on_resolver_changed)
 
     def _on_resolver_removed(self, k: str) -> None:
         try:
@@ -427,6 +482,9 @@ class ConnectionPool(FSM):
             raise AssertionError("resolver key %s not found" % k)
         self.p_backends.pop(k, None)
         self.p_dead.pop(k, None)
+        if self.p_ranks is not None:
+            self.p_ranks.pop(k, None)
+            self.p_rank_gen += 1
         # Slots unlink themselves (and rebalance) from the stateChanged
         # handler in add_connection once they stop; here we only flag
         # them unwanted (lib/pool.js:300-313).
@@ -438,8 +496,7 @@ class ConnectionPool(FSM):
         S.valid_transitions(["failed", "running", "stopping"])
         global_monitor.register_pool(self)
 
-        S.on(self.p_resolver, "added", self._on_resolver_added)
-        S.on(self.p_resolver, "removed", self._on_resolver_removed)
+        self._subscribe_resolver(S)
 
         if self.p_resolver.is_in_state("failed"):
             self.p_log.warn('pre-provided resolver has already failed, '
@@ -484,8 +541,7 @@ class ConnectionPool(FSM):
 
     def state_failed(self, S: StateScope) -> None:
         S.valid_transitions(["running", "stopping"])
-        S.on(self.p_resolver, "added", self._on_resolver_added)
-        S.on(self.p_resolver, "removed", self._on_resolver_removed)
+        self._subscribe_resolver(S)
         S.on(self.p_shuffle_timer, "timeout", self.reshuffle)
 
         def on_connected(*a: Any) -> None:
@@ -508,8 +564,7 @@ class ConnectionPool(FSM):
 
     def state_running(self, S: StateScope) -> None:
         S.valid_transitions(["failed", "stopping"])
-        S.on(self.p_resolver, "added", self._on_resolver_added)
-        S.on(self.p_resolver, "removed", self._on_resolver_removed)
+        self._subscribe_resolver(S)
         S.on(self.p_rebal_timer, "timeout", self.rebalance)
         S.on(self.p_shuffle_timer, "timeout", self.reshuffle)
 
@@ -680,6 +735,10 @@ class ConnectionPool(FSM):
 
         census = (target, tuple(counts), tuple(self.p_keys),
                   tuple(sorted(self.p_dead)))
+        ranks = self.p_ranks
+        if ranks is not None:
+            # a rank edit changes the plan without changing any count
+            census += (self.p_rank_gen,)
         if census == self.p_noop_census:
             self.p_in_rebalance = False
             self.p_last_rebalance = mod_time.time()
@@ -689,7 +748,11 @@ class ConnectionPool(FSM):
         for k in self.p_keys:
             conns[k] = list(self.p_connections.get(k, ()))
 
-        plan = mod_utils.plan_rebalance(conns, self.p_dead, target, self.p_max)
+        plan = mod_utils.plan_rebalance(conns, self.p_dead, target,
+                                        self.p_max, ranks=ranks)
+        if ranks is not None:
+            self._note_active_priority(mod_utils.active_priority(
+                self.p_keys, self.p_dead, ranks))
         self.p_noop_census = None if (plan["remove"] or plan["add"]) \
             else census
 
@@ -751,6 +814,28 @@ class ConnectionPool(FSM):
 
         self.p_in_rebalance = False
         self.p_last_rebalance = mod_time.time()
+
+    def _note_active_priority(self, new: Optional[int]) -> None:
+        old = self.p_active_priority
+        if new == old:
+            return
+        self.p_active_priority = new
+        if old is None or new is None:
+            return  # first backends seen: nothing to fail over from
+        self.p_log.info("failing %s to priority %d"
+                        % ("over" if new > old else "back", new))
+        self._incr_counter("priority-changed")
+        self.emit("priorityChanged", old, new)
+
+    def get_ranking(self) -> Dict[str, Any]:
+        """SRV ranking as the pool sees it: ``{"enabled",
+        "activePriority", "tiers": [{"priority", "backends", "dead",
+        "connections", "weights": {key: weight}}, ...]}``, tiers in
+        ascending priority order; ``{"enabled": False}`` when the pool
+        was created without ``srvRanking``."""
+        return mod_utils.ranking_report(
+            self.p_keys, self.p_dead, self.p_ranks,
+            {k: len(v) for k, v in self.p_connections.items()})
 
     # -- slot lifecycle ----------------------------------------------------
     def add_connection(self, key: str) -> None:

@@ -89,6 +89,8 @@ class ResolverFSM(FSM):
         super().__init__("stopped", loop=options.get("loop"))
         fsm.on("added", lambda k, b: self.emit("added", k, b))
         fsm.on("removed", lambda k: self.emit("removed", k))
+        # only resolvers with srvRanking on ever emit this
+        fsm.on("changed", lambda k, b: self.emit("changed", k, b))
 
     def start(self) -> None:
         self.emit("startAsserted")
@@ -156,11 +158,27 @@ class _StaticResolver(EventEmitter):
                 port = options.get("defaultPort")
             if not isinstance(port, int):
                 raise TypeError("options.backends[%d].port is required" % i)
-            self.sr_backends.append({
+            be = {
                 "name": "%s:%d" % (addr, port),
                 "address": addr,
                 "port": port,
-            })
+            }
+            # optional SRV-style rank, for pools/sets with srvRanking;
+            # emitted only when given
+            for fld in ("priority", "weight"):
+                val = backend.get(fld)
+                if val is None:
+                    continue
+                if not isinstance(val, int) or isinstance(val, bool):
+                    raise TypeError(
+                        "options.backends[%d].%s must be an integer"
+                        % (i, fld))
+                if not 0 <= val <= 65535:
+                    raise ValueError(
+                        "options.backends[%d].%s must be in 0..65535"
+                        % (i, fld))
+                be[fld] = val
+            self.sr_backends.append(be)
         self.sr_state = "idle"
         self._loop = get_loop(options.get("loop"))
 
@@ -230,6 +248,15 @@ class DNSResolverFSM(FSM):
             self.r_defport = 53
             self.r_maxres = options.get("maxDNSConcurrency") or 10
             self.r_ref_count = 0
+
+        # SRV ranking (RFC 2782 priority/weight): opt-in, and never for
+        # bootstrap resolvers, whose consumers want every nameserver
+        srv_ranking = options.get("srvRanking")
+        if srv_ranking is None:
+            srv_ranking = False
+        if not isinstance(srv_ranking, bool):
+            raise TypeError("options.srvRanking must be a bool")
+        self.r_srv_ranking = srv_ranking and not self.r_is_bootstrap
 
         log: CueballLogger = options.get("log") or default_logger()
         self.r_log = log.child(component="DNSResolverFSM",
@@ -724,6 +751,7 @@ class DNSResolverFSM(FSM):
         old_backends = self.r_backends
         new_backends: Dict[str, Dict[str, Any]] = {}
         all_addrs: List[str] = []
+        ranking = self.r_srv_ranking
         for srv in self.r_srvs:
             srv["addresses"] = list(srv.get("addresses_v6") or []) + \
                 list(srv.get("addresses_v4") or [])
@@ -731,7 +759,20 @@ class DNSResolverFSM(FSM):
                 final = {"name": srv["name"], "port": srv["port"],
                          "address": addr}
                 all_addrs.append(addr)
-                new_backends[srv_key(final)] = final
+                k = srv_key(final)
+                if ranking:
+                    # plain-name fallback entries carry no rank: 0/0
+                    final["priority"] = srv.get("priority", 0)
+                    final["weight"] = srv.get("weight", 0)
+                    dup = new_backends.get(k)
+                    # Rank is not part of the key: of several records
+                    # for one backend the best one wins (lowest
+                    # priority, then highest weight).
+                    if dup is not None and \
+                            (dup["priority"], -dup["weight"]) <= \
+                            (final["priority"], -final["weight"]):
+                        continue
+                new_backends[k] = final
 
         if not new_backends:
             err = _verror(self.r_last_error,
@@ -745,6 +786,14 @@ class DNSResolverFSM(FSM):
 
         removed = [k for k in old_backends if k not in new_backends]
         added = [k for k in new_backends if k not in old_backends]
+        changed: List[str] = []
+        if ranking:
+            for k, be in new_backends.items():
+                old = old_backends.get(k)
+                if old is not None and \
+                        (old.get("priority"), old.get("weight")) != \
+                        (be["priority"], be["weight"]):
+                    changed.append(k)
 
         self.r_backends = new_backends
 
@@ -760,6 +809,10 @@ class DNSResolverFSM(FSM):
             self.r_log.trace("host added: %s", k)
             self.emit("added", k, new_backends[k])
             self._incr_counter("backend-added")
+        for k in changed:
+            self.r_log.trace("host rank changed: %s", k)
+            self.emit("changed", k, new_backends[k])
+            self._incr_counter("backend-changed")
 
         if self.r_is_bootstrap:
             gone = [r for r in self.r_resolvers if r not in all_addrs]
@@ -894,6 +947,9 @@ class DNSResolverFSM(FSM):
                         min_ttl = a["ttl"]
                     obj: Dict[str, Any] = {"name": a["target"],
                                            "port": a["port"]}
+                    if self.r_srv_ranking:
+                        obj["priority"] = a.get("priority", 0)
+                        obj["weight"] = a.get("weight", 0)
                     if a["target"] in cache:
                         self._incr_counter("additionals-used")
                         obj["additionals"] = cache[a["target"]]

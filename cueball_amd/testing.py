@@ -197,6 +197,15 @@ class DummyResolver(EventEmitter):
         self.backends.pop(key, None)
         self.emit("removed", key)
 
+    def change(self, key: str, **fields: Any) -> None:
+        """Re-rank a known backend (``priority=``/``weight=``) the way
+        a DNS resolver with srvRanking does: same key, a fresh backend
+        dict, one 'changed' event."""
+        backend = dict(self.backends[key])
+        backend.update(fields)
+        self.backends[key] = backend
+        self.emit("changed", key, backend)
+
     def fail(self, err: BaseException) -> None:
         self._last_error = err
         self.state = "failed"
@@ -343,10 +352,11 @@ class MockDnsServer:
 
     # -- zone building --------------------------------------------------
     def add_srv(self, name: str, target: str, port: int,
-                ttl: int = 60) -> None:
+                ttl: int = 60, priority: int = 0,
+                weight: int = 10) -> None:
         self.zone.setdefault((name.lower(), "SRV"), []).append({
-            "type": "SRV", "name": name, "ttl": ttl, "priority": 0,
-            "weight": 10, "port": port, "target": target})
+            "type": "SRV", "name": name, "ttl": ttl, "priority": priority,
+            "weight": weight, "port": port, "target": target})
 
     def add_a(self, name: str, address: str, ttl: int = 60) -> None:
         self.zone.setdefault((name.lower(), "A"), []).append({

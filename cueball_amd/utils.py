@@ -23,6 +23,8 @@ from . import metrics as mod_metrics
 __all__ = [
     "shuffle",
     "plan_rebalance",
+    "active_priority",
+    "ranking_report",
     "assert_recovery",
     "assert_recovery_set",
     "assert_claim_delay",
@@ -206,7 +208,9 @@ def assert_claim_delay(delay: Any) -> None:
 def plan_rebalance(connections: Mapping[str, Sequence[Any]],
                    dead: Mapping[str, bool],
                    target: int, maximum: int,
-                   singleton: bool = False) -> Dict[str, List[Any]]:
+                   singleton: bool = False,
+                   ranks: Optional[Mapping[str, Sequence[int]]] = None
+                   ) -> Dict[str, List[Any]]:
     """Compute the add/remove plan that takes the pool to an even spread.
 
     Semantics (reference lib/utils.js:239-393): round-robin ``target``
@@ -218,8 +222,15 @@ def plan_rebalance(connections: Mapping[str, Sequence[Any]],
     double-replacement.  With ``singleton`` (Sets), at most one
     connection per distinct backend.
 
+    With ``ranks`` (key -> (priority, weight), SRV ranking) only the
+    active priority tier is spread, by weight; see
+    ``_plan_rebalance_ranked``.  ``ranks=None`` never looks at rank data.
+
     Returns {"add": [backend keys...], "remove": [connection objects...]}.
     """
+    if ranks is not None:
+        return _plan_rebalance_ranked(connections, dead, target, maximum,
+                                      singleton, ranks)
     if target < 0:
         raise ValueError("target must be >= 0")
     if maximum < target:
@@ -326,6 +337,234 @@ def plan_rebalance(connections: Mapping[str, Sequence[Any]],
             have += 1
 
     return plan
+
+def _diff_plan(connections: Mapping[str, Sequence[Any]],
+               wanted: Mapping[str, int]) -> Dict[str, List[Any]]:
+    """Diff what we have against what we want.  Removals prefer backends
+    at the tail of the preference list, and remove the oldest connections
+    first; adds go in preference order."""
+    plan: Dict[str, List[Any]] = {"add": [], "remove": []}
+    fwd = list(connections.keys())
+    for key in reversed(fwd):
+        lst = list(connections.get(key) or ())
+        have = len(lst)
+        want = wanted.get(key, 0)
+        while have > want:
+            plan["remove"].append(lst.pop(0))
+            have -= 1
+    for key in fwd:
+        have = len(connections.get(key) or ())
+        want = wanted.get(key, 0)
+        while have < want:
+            plan["add"].append(key)
+            have += 1
+    return plan
+
+
+def active_priority(keys: Sequence[str], dead: Mapping[str, bool],
+                    ranks: Mapping[str, Sequence[int]]) -> Optional[int]:
+    """The SRV priority tier a pool or set should be using: the lowest
+    priority value with at least one backend not declared dead, or, when
+    every backend is dead, the lowest priority present.  None without
+    backends.  Keys missing from ``ranks`` rank as (0, 0)."""
+    lowest: Optional[int] = None
+    lowest_alive: Optional[int] = None
+    for k in keys:
+        prio = ranks[k][0] if k in ranks else 0
+        if lowest is None or prio < lowest:
+            lowest = prio
+        if not dead.get(k, False) and \
+                (lowest_alive is None or prio < lowest_alive):
+            lowest_alive = prio
+    return lowest_alive if lowest_alive is not None else lowest
+
+
+def ranking_report(keys: Sequence[str], dead: Mapping[str, bool],
+                   ranks: Optional[Mapping[str, Sequence[int]]],
+                   connections: Mapping[str, int]) -> Dict[str, Any]:
+    """The body of ``get_ranking()`` for pools and sets: backends
+    grouped into priority tiers, ascending.  ``connections`` maps key ->
+    live connection count."""
+    if ranks is None:
+        return {"enabled": False}
+    tiers: Dict[int, Dict[str, Any]] = {}
+    for k in keys:
+        prio, weight = ranks[k] if k in ranks else (0, 0)
+        t = tiers.get(prio)
+        if t is None:
+            t = tiers[prio] = {"priority": prio, "backends": 0, "dead": 0,
+                               "connections": 0, "weights": {}}
+        t["backends"] += 1
+        if dead.get(k, False):
+            t["dead"] += 1
+        t["connections"] += connections.get(k, 0)
+        t["weights"][k] = weight
+    return {
+        "enabled": True,
+        "activePriority": active_priority(keys, dead, ranks),
+        "tiers": [tiers[p] for p in sorted(tiers)],
+    }
+
+
+class _WeightedCycle:
+    """Key source of the ranked planner: smooth weighted round-robin
+    over one tier, in preference order.  Every ``next()`` adds each
+    key's weight to its running score, takes the highest score (ties to
+    the earliest key) and subtracts the total from the winner, so over
+    any ``sum(weights)`` consecutive steps key i is returned exactly
+    ``weights[i]`` times, interleaved, not in runs.  With equal weights
+    this is plain round-robin."""
+
+    __slots__ = ("keys", "weights", "scores", "total")
+
+    def __init__(self, keys: Sequence[str], weights: Sequence[int]) -> None:
+        self.keys = list(keys)
+        self.weights = list(weights)
+        self.scores = [0] * len(self.keys)
+        self.total = sum(self.weights)
+
+    def next(self) -> str:
+        scores = self.scores
+        best = 0
+        for i, w in enumerate(self.weights):
+            scores[i] += w
+            if scores[i] > scores[best]:
+                best = i
+        scores[best] -= self.total
+        return self.keys[best]
+
+
+def _plan_rebalance_ranked(connections: Mapping[str, Sequence[Any]],
+                           dead: Mapping[str, bool],
+                           target: int, maximum: int, singleton: bool,
+                           ranks: Mapping[str, Sequence[int]]
+                           ) -> Dict[str, List[Any]]:
+    """``plan_rebalance`` with SRV ranks (RFC 2782).
+
+    Only the active tier (``active_priority``) carries load.  Tiers
+    numbered below it are dead by construction and get one slot each,
+    their monitor, so the pool can fail back; at most ``maximum - 1`` of
+    those, so the active tier always keeps a slot.  Tiers numbered above
+    it get nothing.  The two passes of ``plan_rebalance`` then run over
+    the active tier alone, with what is left of ``maximum``, drawing
+    keys from a ``_WeightedCycle`` instead of the plain rotation.
+
+    A key's weight in the cycle is ``max(weight, 1)`` over the tier's
+    gcd (weight 0 means "very small share", not "never"), except that a
+    dead backend always counts 1 (it only needs its monitor, and its
+    share flows to the replacements) and in ``singleton`` mode every key
+    counts 1 and the tier is visited heaviest first.  Both exceptions
+    also keep the number of steps independent of the weights.  With all
+    ranks equal the plan is exactly that of ``ranks=None``.
+    """
+    if target < 0:
+        raise ValueError("target must be >= 0")
+    if maximum < target:
+        raise ValueError("max must be >= target")
+
+    all_keys = list(connections.keys())
+    wanted: Dict[str, int] = {}
+    if not all_keys:
+        return {"add": [], "remove": []}
+
+    def rank(k: str) -> Sequence[int]:
+        return ranks[k] if k in ranks else (0, 0)
+
+    active = active_priority(all_keys, dead, ranks)
+
+    # Monitor slots for the tiers we failed away from.
+    lower = sorted((k for k in all_keys if rank(k)[0] < active),
+                   key=lambda k: rank(k)[0])
+    monitors = lower[:max(maximum - 1, 0)]
+    for k in monitors:
+        wanted[k] = 1
+    maximum -= len(monitors)
+    if target > maximum:
+        target = maximum
+
+    tier = [k for k in all_keys if rank(k)[0] == active]
+    if singleton:
+        tier.sort(key=lambda k: -max(rank(k)[1], 1))
+        weights = [1] * len(tier)
+    else:
+        raw = [max(rank(k)[1], 1) for k in tier]
+        div = math.gcd(*raw)
+        weights = [1 if dead.get(k, False) else w // div
+                   for k, w in zip(tier, raw)]
+    cycle = _WeightedCycle(tier, weights)
+
+    replacements = 0
+    done = 0
+
+    # Pass 1: spread `target` connections by weight; dead backends get
+    # exactly one (the monitor) and queue a replacement.
+    for _ in range(target):
+        k = cycle.next()
+        if k not in wanted:
+            wanted[k] = 0
+        if not dead.get(k, False):
+            if singleton:
+                if wanted[k] == 0:
+                    wanted[k] = 1
+                    done += 1
+            else:
+                wanted[k] += 1
+                done += 1
+            continue
+        if wanted[k] == 0:
+            wanted[k] = 1
+            done += 1
+        replacements += 1
+
+    if done + replacements > maximum:
+        replacements = maximum - done
+
+    # Pass 2: allocate replacements, with the same starvation control
+    # under the max cap as plan_rebalance.
+    i = 0
+    while i < replacements:
+        k = cycle.next()
+        if k not in wanted:
+            wanted[k] = 0
+        alive = not dead.get(k, False)
+        if alive:
+            if singleton:
+                if wanted[k] == 0:
+                    wanted[k] = 1
+                    done += 1
+                    i += 1
+                    continue
+            else:
+                wanted[k] += 1
+                done += 1
+                i += 1
+                continue
+
+        count = done + replacements - i
+        if singleton:
+            empties = [kk for kk in tier
+                       if not dead.get(kk, False) and kk not in wanted]
+        else:
+            empties = [kk for kk in tier
+                       if not dead.get(kk, False) or kk not in wanted]
+
+        if count + 1 <= maximum:
+            if wanted[k] == 0:
+                wanted[k] = 1
+                done += 1
+            if empties:
+                replacements += 1
+        elif count <= maximum and empties:
+            replacements += 1
+        elif count <= maximum:
+            if wanted[k] == 0:
+                wanted[k] = 1
+                done += 1
+        else:
+            break
+        i += 1
+
+    return _diff_plan(connections, wanted)
 
 
 def create_error_metrics(options: Mapping[str, Any]) -> mod_metrics.Collector:
