@@ -102,6 +102,10 @@ class Agent(EventEmitter):
         if srv_ranking is not None and not isinstance(srv_ranking, bool):
             raise TypeError("options.srvRanking must be a bool")
         self.cba_srv_ranking = bool(srv_ranking)
+        # likewise handed to every pool; validated here so that a bad
+        # value fails at construction, not at the first request
+        self.cba_max_conn_age, self.cba_conn_age_spread = \
+            mod_utils.assert_connection_age(options)
 
         for host in options.get("initialDomains") or ():
             self._add_pool(host, {})
@@ -204,6 +208,9 @@ class Agent(EventEmitter):
             pool_opts["latencyStats"] = self.cba_latency_stats
         if self.cba_srv_ranking:
             pool_opts["srvRanking"] = True
+        if self.cba_max_conn_age is not None:
+            pool_opts["maxConnectionAge"] = self.cba_max_conn_age
+            pool_opts["connectionAgeSpread"] = self.cba_conn_age_spread
         if self.cba_ping is not None:
             pool_opts["checkTimeout"] = self.cba_ping_interval or 30000
             pool_opts["checker"] = \
@@ -224,6 +231,17 @@ class Agent(EventEmitter):
         """Per-host ``ConnectionPool.get_latency_stats()``."""
         return {host: pool.get_latency_stats()
                 for host, pool in self.pools.items()}
+
+    def recycle(self, host: Optional[str] = None) -> int:
+        """``ConnectionPool.recycle()`` on one host's pool, or on every
+        pool when `host` is None; returns the total number of
+        connections marked."""
+        if host is not None:
+            pool = self.pools.get(host)
+            if pool is None:
+                raise CueballError('No pool for host "%s"' % host)
+            return pool.recycle()
+        return sum(pool.recycle() for pool in self.pools.values())
 
     def create_pool(self, host: str,
                     options: Optional[Dict[str, Any]] = None) -> None:

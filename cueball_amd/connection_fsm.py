@@ -68,6 +68,10 @@ def _call_optional(obj: Any, *names: str) -> None:
 class SocketMgrFSM(FSM):
     """Socket lifecycle + retry/backoff engine (1:1 with a slot FSM)."""
 
+    #: loop time at which the current socket entered 'connected' (the
+    #: start of its age; see ConnectionPool maxConnectionAge)
+    sm_connected_at: Optional[float] = None
+
     def __init__(self, options: Dict[str, Any]) -> None:
         recovery = options["recovery"]
         connect_recov = recovery["default"]
@@ -257,6 +261,7 @@ class SocketMgrFSM(FSM):
         S.valid_transitions(["error", "closed"])
         sock = self.sm_socket
         self.sm_log.trace("connected")
+        self.sm_connected_at = self._loop.time()
         self.reset_backoff()
 
         def on_error(err: BaseException) -> None:

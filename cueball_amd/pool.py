@@ -175,6 +175,22 @@ class ConnectionPool(FSM):
     p_active_priority: Optional[int] = None
     _prio_gauge = None
 
+    # Connection age / recycle() state, class-level for the same
+    # reason: a pool without maxConnectionAge that never called
+    # recycle() has none of these in its instance dict.
+    p_age_max: Optional[float] = None      # maxConnectionAge, ms
+    p_age_spread: Optional[float] = None
+    #: slot -> [deadline (loop seconds), reason] for connected sockets
+    #: that have a deadline; None until the feature is in use
+    p_age_slots: Optional[Dict[Any, list]] = None
+    #: slot -> reason for slots retired or marked, until they stop
+    p_age_retiring: Optional[Dict[Any, str]] = None
+    #: retired slots that stopped whose replacement is not planned yet
+    p_age_settling = 0
+    p_age_timer = None
+    p_age_timer_at: Optional[float] = None
+    _age_gauge = None
+
     def __init__(self, options: Dict[str, Any]) -> None:
         if not callable(options.get("constructor")):
             raise TypeError("options.constructor (callable) is required")
@@ -305,6 +321,22 @@ class ConnectionPool(FSM):
                     help="SRV priority tier the pool is currently using")
             except (AttributeError, ValueError):
                 pass
+
+        # Connection age (opt-in): see the "connection age" section
+        # below.  Off means not one attribute is set here.
+        age, spread = mod_utils.assert_connection_age(options)
+        if age is not None:
+            self.p_age_max = age
+            self.p_age_spread = spread
+            self.p_age_slots = {}
+            self.p_age_retiring = {}
+            if self._gauge is not None:
+                try:
+                    self._age_gauge = self.p_collector.gauge(
+                        name="cueball_pool_oldest_connection_seconds",
+                        help="Age of the pool's oldest connected socket")
+                except (AttributeError, ValueError):
+                    pass
 
         if options.get("resolver") is not None:
             self.p_resolver = options["resolver"]
@@ -440,6 +472,10 @@ class ConnectionPool(FSM):
         if self._prio_gauge is not None and \
                 self.p_active_priority is not None:
             self._prio_gauge.set(self.p_active_priority, self._gauge_labels)
+        if self._age_gauge is not None:
+            oldest = self._age_oldest(self._loop.time())
+            self._age_gauge.set(0.0 if oldest is None else oldest,
+                                self._gauge_labels)
         if self.p_last_rebal_clamped:
             self.rebalance()
 
@@ -578,9 +614,16 @@ class ConnectionPool(FSM):
 
         S.on(self, "closedBackend", on_closed_backend)
         S.on(self, "stopAsserted", lambda: S.goto_state("stopping"))
+        if self.p_age_slots is not None:
+            # deadlines that passed while the pool was not running
+            self._loop.call_soon(self._age_run)
 
     def state_stopping(self, S: StateScope) -> None:
         S.valid_transitions(["stopping.backends"])
+        if self.p_age_timer is not None:
+            self.p_age_timer.cancel()
+            self.p_age_timer = None
+            self.p_age_timer_at = None
         # Divergence from the reference (bug fix): fail queued waiters
         # with PoolStoppingError instead of leaving them pending forever
         # (the reference's state_stopping never touches p_waiters, so an
@@ -837,6 +880,192 @@ class ConnectionPool(FSM):
             self.p_keys, self.p_dead, self.p_ranks,
             {k: len(v) for k, v in self.p_connections.items()})
 
+    # -- connection age / recycle() ------------------------------------------
+    #
+    # Every connected socket may carry a deadline: its connect time plus
+    # a lifetime drawn once per socket (maxConnectionAge), or "now"
+    # (recycle()).  One call_at timer waits for the earliest deadline
+    # still ahead; everything else is driven by events the pool sees
+    # anyway: a socket manager connecting, a slot stopping or failing.
+    # Retirement is set_unwanted() on the slot, so the replacement is
+    # the ordinary rebalance's business.  None of this is reachable
+    # from claim() or from the slot's busy/idle cycle.
+
+    def _age_watch(self, fsm: ConnectionSlotFSM) -> None:
+        fsm.csf_smgr.on("stateChanged",
+                        functools.partial(self._age_smgr_changed, fsm))
+
+    def _age_smgr_changed(self, fsm: ConnectionSlotFSM, st: str) -> None:
+        if st == "connected":
+            smgr = fsm.csf_smgr
+            if smgr.is_in_state("connected") and \
+                    fsm not in self.p_age_retiring:
+                if self.p_age_max is not None:
+                    life = self.p_age_max * \
+                        (1.0 - self.p_age_spread * random.random())
+                    self.p_age_slots[fsm] = [
+                        smgr.sm_connected_at + life / 1000.0, "age"]
+                else:
+                    # a new socket: a recycle() mark was for the old one
+                    self.p_age_slots.pop(fsm, None)
+            # Next turn: the slot itself has not seen this event yet
+            # and still counts as connecting.
+            self._loop.call_soon(self._age_run)
+        elif st == "error" or st == "closed":
+            self.p_age_slots.pop(fsm, None)
+
+    def _age_slot_gone(self, fsm: ConnectionSlotFSM) -> None:
+        """A slot stopped or failed.  Held-back retirements are looked
+        at again once the rebalance this just scheduled has run, so
+        that a replacement it opens is seen as in flight."""
+        self.p_age_slots.pop(fsm, None)
+        self.p_age_retiring.pop(fsm, None)
+        self.p_age_settling += 1
+        self._loop.call_soon(self._age_settled)
+
+    def _age_settled(self) -> None:
+        self.p_age_settling -= 1
+        self._age_run()
+
+    def _age_in_flight(self) -> bool:
+        if self.p_age_settling > 0:
+            return True
+        for fsm in self.p_age_retiring:
+            # a marked lease counts once it begins stopping
+            if fsm._fsm_state != "busy":
+                return True
+        for conns in self.p_connections.values():
+            for fsm in conns:
+                if not fsm.csf_monitor and fsm._fsm_state in (
+                        "init", "connecting", "retrying"):
+                    return True
+        return False
+
+    def _age_timer_fired(self) -> None:
+        at = self.p_age_timer_at
+        self.p_age_timer = None
+        self.p_age_timer_at = None
+        # a loop may fire a timer a clock tick early
+        self._age_run(max(self._loop.time(), at))
+
+    def _age_run(self, now: Optional[float] = None) -> None:
+        """Retire what is due: every busy slot is marked, idle slots go
+        oldest deadline first and one at a time.  Then re-arm the timer."""
+        if self._fsm_state != "running":
+            return
+        if now is None:
+            now = self._loop.time()
+        slots = self.p_age_slots
+        due = [(ent[0], i, fsm) for i, (fsm, ent) in
+               enumerate(slots.items()) if ent[0] <= now]
+        if due:
+            due.sort()
+            blocked: Optional[bool] = None
+            for _, _, fsm in due:
+                st = fsm._fsm_state
+                if st == "busy":
+                    self._age_retire(fsm, now)
+                elif st == "idle":
+                    if blocked is None:
+                        blocked = self._age_in_flight()
+                    if not blocked:
+                        self._age_retire(fsm, now)
+                        blocked = True
+                # any other state is on its way somewhere: the event
+                # that ends it brings us back here
+        nxt: Optional[float] = None
+        for ent in slots.values():
+            if ent[0] > now and (nxt is None or ent[0] < nxt):
+                nxt = ent[0]
+        if nxt != self.p_age_timer_at:
+            if self.p_age_timer is not None:
+                self.p_age_timer.cancel()
+                self.p_age_timer = None
+            if nxt is not None:
+                self.p_age_timer = self._loop.call_at(
+                    nxt, self._age_timer_fired)
+            self.p_age_timer_at = nxt
+
+    def _age_retire(self, fsm: ConnectionSlotFSM, now: float) -> None:
+        reason = self.p_age_slots.pop(fsm)[1]
+        self.p_age_retiring[fsm] = reason
+        key = fsm.csf_backend.get("key")
+        at = fsm.csf_smgr.sm_connected_at
+        fsm.csf_log.info(
+            'recycling connection to backend "%s" (%s) at age %d ms',
+            key, reason, round((now - at) * 1000.0) if at is not None else 0)
+        self._incr_counter("recycled-" + reason)
+        # idle: stops now; busy: stops when its lease is released
+        fsm.set_unwanted()
+        self.emit("connectionRecycled", key, reason)
+
+    def _age_oldest(self, now: float) -> Optional[float]:
+        """Age in seconds of the oldest connected socket, or None."""
+        oldest: Optional[float] = None
+        for conns in self.p_connections.values():
+            for fsm in conns:
+                smgr = fsm.csf_smgr
+                if smgr._fsm_state == "connected":
+                    age = now - smgr.sm_connected_at
+                    if oldest is None or age > oldest:
+                        oldest = age
+        return oldest
+
+    def recycle(self) -> int:
+        """Treat every socket connected right now as expired: idle ones
+        are retired one at a time, each after the previous one's
+        replacement connected; claimed ones when their lease is
+        released.  Connections opened later are unaffected.  Returns
+        the number of connections marked (0 once the pool is stopping,
+        stopped or failed)."""
+        if self._fsm_state not in ("starting", "running"):
+            return 0
+        if self.p_age_slots is None:
+            self.p_age_slots = {}
+            self.p_age_retiring = {}
+            for conns in self.p_connections.values():
+                for fsm in conns:
+                    self._age_watch(fsm)
+        now = self._loop.time()
+        marked = 0
+        for conns in self.p_connections.values():
+            for fsm in conns:
+                if fsm in self.p_age_retiring or \
+                        fsm.csf_smgr._fsm_state != "connected":
+                    continue
+                ent = self.p_age_slots.get(fsm)
+                at = now if ent is None or ent[0] > now else ent[0]
+                self.p_age_slots[fsm] = [at, "manual"]
+                marked += 1
+        self._age_run(now)
+        return marked
+
+    def get_connection_ages(self) -> Dict[str, Any]:
+        """``{"maxAgeMs", "oldestMs", "connections": [{"backend",
+        "state", "ageMs", "expiresInMs", "recycling"}, ...]}``; ages
+        and expiries are None for a slot without a connected socket,
+        ``expiresInMs`` also for a socket without a deadline."""
+        now = self._loop.time()
+        slots = self.p_age_slots or {}
+        retiring = self.p_age_retiring or {}
+        out = []
+        for k, conns in self.p_connections.items():
+            for fsm in conns:
+                smgr = fsm.csf_smgr
+                age = expires = None
+                if smgr._fsm_state == "connected":
+                    age = (now - smgr.sm_connected_at) * 1000.0
+                    ent = slots.get(fsm)
+                    if ent is not None:
+                        expires = max(0.0, (ent[0] - now) * 1000.0)
+                out.append({"backend": k, "state": fsm.get_state(),
+                            "ageMs": age, "expiresInMs": expires,
+                            "recycling": fsm in retiring})
+        oldest = self._age_oldest(now)
+        return {"maxAgeMs": self.p_age_max,
+                "oldestMs": None if oldest is None else oldest * 1000.0,
+                "connections": out}
+
     # -- slot lifecycle ----------------------------------------------------
     def add_connection(self, key: str) -> None:
         if self.is_in_state("stopping") or self.is_in_state("stopped"):
@@ -871,6 +1100,8 @@ class ConnectionPool(FSM):
         else:
             fsm.on("stateChanged",
                    functools.partial(self._slot_state_changed, fsm, key))
+        if self.p_age_slots is not None:
+            self._age_watch(fsm)
         fsm.start()
 
     def _slot_state_changed(self, fsm: ConnectionSlotFSM, key: str,
@@ -939,6 +1170,8 @@ class ConnectionPool(FSM):
                     del self.p_connections[key]
             self.emit("closedBackend", key, fsm)
             self.rebalance()
+            if self.p_age_slots is not None:
+                self._age_slot_gone(fsm)
 
         if fsm.p_idleq_node is not None:
             # Was idle, now isn't: unlink and rebalance in case we were

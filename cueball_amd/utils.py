@@ -205,6 +205,33 @@ def assert_claim_delay(delay: Any) -> None:
         raise ValueError("targetClaimDelay must be a positive integer")
 
 
+def assert_connection_age(options: Mapping[str, Any]) -> tuple:
+    """Validate ``maxConnectionAge`` (ms, finite, > 0) and
+    ``connectionAgeSpread`` (fraction in [0, 1), default 0.2); returns
+    ``(age, spread)``, ``(None, None)`` when the option is off.  A
+    spread without an age is an error."""
+    age = options.get("maxConnectionAge")
+    spread = options.get("connectionAgeSpread")
+    if age is not None:
+        if not _num(age):
+            raise TypeError("options.maxConnectionAge must be a number")
+        if not math.isfinite(age) or age <= 0:
+            raise ValueError("options.maxConnectionAge must be finite "
+                             "and > 0")
+    if spread is not None:
+        if not _num(spread):
+            raise TypeError("options.connectionAgeSpread must be a number")
+        if not math.isfinite(spread) or spread < 0 or spread >= 1:
+            raise ValueError("options.connectionAgeSpread must be in "
+                             "[0, 1)")
+        if age is None:
+            raise ValueError("options.connectionAgeSpread needs "
+                             "options.maxConnectionAge")
+    if age is None:
+        return (None, None)
+    return (age, 0.2 if spread is None else spread)
+
+
 def plan_rebalance(connections: Mapping[str, Sequence[Any]],
                    dead: Mapping[str, bool],
                    target: int, maximum: int,
