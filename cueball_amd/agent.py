@@ -106,6 +106,12 @@ class Agent(EventEmitter):
         # value fails at construction, not at the first request
         self.cba_max_conn_age, self.cba_conn_age_spread = \
             mod_utils.assert_connection_age(options)
+        # Likewise.  An agent closes leases on purpose (non-keep-alive
+        # responses, aborts) and releases after the socket closed, so
+        # by default neither counts against a backend: what does is a
+        # socket error under a request and a failed ping.
+        self.cba_outlier = mod_utils.assert_outlier_detection(
+            options, count_default=False)
 
         for host in options.get("initialDomains") or ():
             self._add_pool(host, {})
@@ -211,6 +217,8 @@ class Agent(EventEmitter):
         if self.cba_max_conn_age is not None:
             pool_opts["maxConnectionAge"] = self.cba_max_conn_age
             pool_opts["connectionAgeSpread"] = self.cba_conn_age_spread
+        if self.cba_outlier is not None:
+            pool_opts["outlierDetection"] = dict(self.cba_outlier)
         if self.cba_ping is not None:
             pool_opts["checkTimeout"] = self.cba_ping_interval or 30000
             pool_opts["checker"] = \
@@ -242,6 +250,26 @@ class Agent(EventEmitter):
                 raise CueballError('No pool for host "%s"' % host)
             return pool.recycle()
         return sum(pool.recycle() for pool in self.pools.values())
+
+    def get_outlier_stats(self) -> Dict[str, Any]:
+        """Per-host ``ConnectionPool.get_outlier_stats()``."""
+        return {host: pool.get_outlier_stats()
+                for host, pool in self.pools.items()}
+
+    def _pool_for(self, host: str) -> ConnectionPool:
+        pool = self.pools.get(host)
+        if pool is None:
+            raise CueballError('No pool for host "%s"' % host)
+        return pool
+
+    def eject_backend(self, host: str, key: str,
+                      ms: Optional[float] = None) -> bool:
+        """``ConnectionPool.eject_backend(key, ms)`` on `host`'s pool."""
+        return self._pool_for(host).eject_backend(key, ms)
+
+    def reinstate_backend(self, host: str, key: str) -> bool:
+        """``ConnectionPool.reinstate_backend(key)`` on `host`'s pool."""
+        return self._pool_for(host).reinstate_backend(key)
 
     def create_pool(self, host: str,
                     options: Optional[Dict[str, Any]] = None) -> None:

@@ -321,6 +321,20 @@ class SocketMgrFSM(FSM):
         self.sm_pool._incr_counter("retries-exhausted")
 
 
+def _report_failure(handle: Any, err: Optional[BaseException]) -> None:
+    """ClaimHandle.report_failure(), shared by both claim handles: the
+    claimer judged this lease failed at protocol level (say an HTTP 503
+    on a healthy socket).  Only a mark on the handle; the pool's outlier
+    detection reads it when the lease has ended."""
+    if handle._fsm_state != "claimed":
+        raise mod_errors.CueballError(
+            'ClaimHandle.report_failure() called while in state "%s"'
+            % handle.get_state())
+    handle.ch_failure_reported = True
+    if err is not None:
+        handle.ch_log.debug("claimer reported the lease as failed: %r", err)
+
+
 class ClaimHandle(FSM):
     """Handle given to pool users; drives the claim double-handshake.
 
@@ -343,6 +357,9 @@ class ClaimHandle(FSM):
     ch_pre_listeners: Any = None
     #: claim time of a handle whose wait was recorded (None otherwise)
     ch_claimed_at: Optional[float] = None
+    #: set by report_failure(): the lease counts as failed for the
+    #: pool's outlier detection, however it ends
+    ch_failure_reported = False
 
     def __init__(self, options: Dict[str, Any]) -> None:
         self.ch_claim_timeout = options["claimTimeout"]
@@ -483,6 +500,9 @@ class ClaimHandle(FSM):
 
     def close(self) -> None:
         self._relinquish("closed")
+
+    def report_failure(self, err: Optional[BaseException] = None) -> None:
+        _report_failure(self, err)
 
     # -- states ----------------------------------------------------------
     def state_waiting(self, S: StateScope) -> None:
@@ -649,6 +669,12 @@ if _native_count is not None:
             self._setup(pool, claim_stack, callback, log,
                         float(claim_timeout), True, loop)
             return self
+
+        ch_failure_reported = False
+
+        def report_failure(self,
+                           err: Optional[BaseException] = None) -> None:
+            _report_failure(self, err)
 
 
 def count_listeners(emitter: Any, event: str) -> int:

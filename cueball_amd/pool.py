@@ -191,6 +191,24 @@ class ConnectionPool(FSM):
     p_age_timer_at: Optional[float] = None
     _age_gauge = None
 
+    # Outlier detection / eject_backend() state, class-level once more:
+    # a pool without outlierDetection that never called eject_backend()
+    # has none of these in its instance dict.
+    #: the validated outlierDetection option, defaults filled in
+    p_od: Optional[Dict[str, Any]] = None
+    #: key -> per-backend record (see _od_record); None until in use
+    p_od_backends: Optional[Dict[str, Dict[str, Any]]] = None
+    #: key -> ejection entry {"reason", "at", "until", "durationMs",
+    #: "timer"} for the backends that are ejected right now
+    p_od_ejected: Optional[Dict[str, Dict[str, Any]]] = None
+    #: slot -> claim handle of the lease seen to begin on it
+    p_od_open: Optional[Dict[Any, Any]] = None
+    #: slot -> last handle attributed to it (a handle has one lease)
+    p_od_last: Optional[Dict[Any, Any]] = None
+    #: slot -> "error" | "closed": how its current socket ended
+    p_od_sock: Optional[Dict[Any, str]] = None
+    _od_gauge = None
+
     def __init__(self, options: Dict[str, Any]) -> None:
         if not callable(options.get("constructor")):
             raise TypeError("options.constructor (callable) is required")
@@ -338,6 +356,23 @@ class ConnectionPool(FSM):
                 except (AttributeError, ValueError):
                     pass
 
+        # Outlier detection (opt-in): see the "outlier ejection"
+        # section below.  Off means not one attribute is set here.
+        od = mod_utils.assert_outlier_detection(options)
+        if od is not None:
+            self.p_od = od
+            self._od_init()
+            self.p_od_open = {}
+            self.p_od_last = {}
+            self.p_od_sock = {}
+            if self._gauge is not None:
+                try:
+                    self._od_gauge = self.p_collector.gauge(
+                        name="cueball_pool_ejected_backends",
+                        help="Backends the pool has ejected as outliers")
+                except (AttributeError, ValueError):
+                    pass
+
         if options.get("resolver") is not None:
             self.p_resolver = options["resolver"]
             self.p_resolver_custom = True
@@ -476,6 +511,8 @@ class ConnectionPool(FSM):
             oldest = self._age_oldest(self._loop.time())
             self._age_gauge.set(0.0 if oldest is None else oldest,
                                 self._gauge_labels)
+        if self._od_gauge is not None:
+            self._od_gauge.set(len(self.p_od_ejected), self._gauge_labels)
         if self.p_last_rebal_clamped:
             self.rebalance()
 
@@ -521,11 +558,21 @@ class ConnectionPool(FSM):
         if self.p_ranks is not None:
             self.p_ranks.pop(k, None)
             self.p_rank_gen += 1
+        if self.p_od_backends is not None:
+            # gone is gone: no event, and a backend that comes back
+            # under the same key starts clean
+            self.p_od_backends.pop(k, None)
+            ent = self.p_od_ejected.pop(k, None)
+            if ent is not None:
+                ent["timer"].cancel()
         # Slots unlink themselves (and rebalance) from the stateChanged
         # handler in add_connection once they stop; here we only flag
         # them unwanted (lib/pool.js:300-313).
         for fsm in list(self.p_connections.get(k, ())):
             fsm.set_unwanted()
+        if self.p_od_ejected:
+            # the last backend that was not ejected may just have left
+            self._od_panic_check()
 
     # -- states ----------------------------------------------------------
     def state_starting(self, S: StateScope) -> None:
@@ -624,6 +671,10 @@ class ConnectionPool(FSM):
             self.p_age_timer.cancel()
             self.p_age_timer = None
             self.p_age_timer_at = None
+        if self.p_od_ejected:
+            for ent in self.p_od_ejected.values():
+                ent["timer"].cancel()
+            self.p_od_ejected.clear()
         # Divergence from the reference (bug fix): fail queued waiters
         # with PoolStoppingError instead of leaving them pending forever
         # (the reference's state_stopping never touches p_waiters, so an
@@ -782,20 +833,30 @@ class ConnectionPool(FSM):
         if ranks is not None:
             # a rank edit changes the plan without changing any count
             census += (self.p_rank_gen,)
+        ejected = self.p_od_ejected
+        if ejected:
+            # an ejection changes the plan without changing any count
+            census += (tuple(sorted(ejected)),)
         if census == self.p_noop_census:
             self.p_in_rebalance = False
             self.p_last_rebalance = mod_time.time()
             return
 
+        # An ejected backend gets no connections at all: the planner
+        # never sees its key (its slots are unwanted and on their way
+        # out already).
+        keys = self.p_keys
+        if ejected:
+            keys = [k for k in keys if k not in ejected]
         conns: Dict[str, List[ConnectionSlotFSM]] = {}
-        for k in self.p_keys:
+        for k in keys:
             conns[k] = list(self.p_connections.get(k, ()))
 
         plan = mod_utils.plan_rebalance(conns, self.p_dead, target,
                                         self.p_max, ranks=ranks)
         if ranks is not None:
             self._note_active_priority(mod_utils.active_priority(
-                self.p_keys, self.p_dead, ranks))
+                keys, self.p_dead, ranks))
         self.p_noop_census = None if (plan["remove"] or plan["add"]) \
             else census
 
@@ -1066,6 +1127,279 @@ class ConnectionPool(FSM):
                 "oldestMs": None if oldest is None else oldest * 1000.0,
                 "connections": out}
 
+    # -- outlier ejection ----------------------------------------------------
+    #
+    # Passive health: a backend that accepts connections but fails the
+    # requests sent over them.  "Dead" (p_dead) means connects fail, and
+    # a monitor slot probes until one succeeds; "ejected" means leases
+    # fail, so a successful connect proves nothing: the backend gets no
+    # connection at all for a fixed time and is then simply tried again.
+    #
+    # Leases are observed from outside the claim path.  A pool with the
+    # option listens to each slot and its socket manager.  stateChanged
+    # is asynchronous, so the listener never trusts the slot's present
+    # state: a lease is pinned to its handle when the slot's 'busy' is
+    # delivered (csf_handle, or csf_prev_handle if the slot has been
+    # released to idle since; the pool cannot hand the slot out again
+    # before it has seen the 'idle' that follows in the same queue), and
+    # judged when the slot's next state is delivered, which says how the
+    # lease left 'busy'.  By then the handle is terminal.
+
+    def _od_init(self) -> None:
+        if self.p_od_backends is None:
+            self.p_od_backends = {}
+            self.p_od_ejected = {}
+
+    def _od_record(self, key: str) -> Dict[str, Any]:
+        rec = self.p_od_backends.get(key)
+        if rec is None:
+            rec = self.p_od_backends[key] = {
+                "streak": 0, "failures": 0, "successes": 0,
+                # consecutive ejections; back to 0 at "cleanAt"
+                "ejections": 0, "cleanAt": None}
+        return rec
+
+    def _od_ejections(self, key: str, rec: Dict[str, Any],
+                      now: float) -> int:
+        """The backend's count of consecutive ejections, forgotten once
+        it has stayed reinstated for as long as its last ejection
+        lasted."""
+        clean_at = rec["cleanAt"]
+        if clean_at is not None and key not in self.p_od_ejected and \
+                now + 1e-9 >= clean_at:
+            rec["ejections"] = 0
+            rec["cleanAt"] = None
+        return rec["ejections"]
+
+    def _od_watch(self, fsm: ConnectionSlotFSM, key: str) -> None:
+        fsm.on("stateChanged",
+               functools.partial(self._od_slot_changed, fsm, key))
+        fsm.csf_smgr.on("stateChanged",
+                        functools.partial(self._od_smgr_changed, fsm))
+
+    def _od_smgr_changed(self, fsm: ConnectionSlotFSM, st: str) -> None:
+        if st == "error" or st == "closed":
+            self.p_od_sock[fsm] = st
+        elif st == "connected":
+            self.p_od_sock.pop(fsm, None)
+
+    def _od_slot_changed(self, fsm: ConnectionSlotFSM, key: str,
+                         st: str) -> None:
+        if st == "busy":
+            hdl = fsm.csf_handle
+            if hdl is None:
+                hdl = fsm.csf_prev_handle
+            # a claim the slot rejected leaves no handle behind, and
+            # csf_prev_handle is then the lease before: judged already
+            if hdl is None or hdl is self.p_od_last.get(fsm) or \
+                    hdl.ch_slot is not fsm or hdl._fsm_state not in (
+                        "claimed", "released", "closed"):
+                return
+            self.p_od_last[fsm] = hdl
+            self.p_od_open[fsm] = hdl
+            return
+        hdl = self.p_od_open.pop(fsm, None)
+        if hdl is not None:
+            self._od_lease_ended(fsm, key, hdl, st)
+        if st == "stopped" or st == "failed":
+            self.p_od_last.pop(fsm, None)
+            self.p_od_sock.pop(fsm, None)
+
+    def _od_lease_ended(self, fsm: ConnectionSlotFSM, key: str, hdl: Any,
+                        nxt: str) -> None:
+        """Judge one lease: `nxt` is the state the slot left 'busy' for.
+        True is a failure, False a success, None neutral."""
+        od = self.p_od
+        closed = hdl._fsm_state == "closed"
+        # How the socket ended, if it did.  The slot may have left
+        # 'busy' as if all were well ('idle', 'stopping', 'killing')
+        # although the socket was gone: a socket that is destroyed on
+        # 'error' emits 'close' from inside the socket manager's
+        # transition, and a claimer that releases on 'close' is then
+        # heard before the socket manager is.  What the socket manager
+        # has reported by now settles it.
+        how = self.p_od_sock.get(fsm)
+        if how == "closed" and (nxt == "killing" or nxt == "stopping"):
+            how = None          # the slot's own doing, on entering `nxt`
+        if how is None:
+            if nxt == "connecting" or nxt == "stopped":
+                how = "closed"
+            elif nxt == "retrying":
+                how = "error"
+        failed: Optional[bool] = None
+        if how == "error":
+            failed = True
+        elif how == "closed":
+            if od["countSocketClose"] or (closed and od["countClose"]):
+                failed = True
+        elif closed:
+            if od["countClose"]:
+                failed = True
+        elif not hdl.ch_pinger:
+            failed = False      # released, socket still connected
+        if closed and hdl.ch_pinger:
+            failed = True       # a failed health check
+        if hdl.ch_failure_reported:
+            failed = True
+        if failed is None or key not in self.p_backends:
+            return
+        rec = self._od_record(key)
+        if not failed:
+            rec["successes"] += 1
+            rec["streak"] = 0
+            return
+        rec["failures"] += 1
+        rec["streak"] += 1
+        if rec["streak"] >= od["consecutiveFailures"] and \
+                key not in self.p_od_ejected:
+            self._od_eject(key, "consecutive-failures", None)
+
+    def _od_usable_without(self, key: str) -> bool:
+        """Would a backend that is neither ejected nor declared dead be
+        left without `key`?"""
+        for k in self.p_keys:
+            if k != key and k not in self.p_od_ejected and \
+                    k not in self.p_dead:
+                return True
+        return False
+
+    def _od_eject(self, key: str, reason: str,
+                  ms: Optional[float]) -> bool:
+        # A lease may outlive the pool's working life (it is held
+        # through 'stopping.backends'); a pool that is winding down or
+        # has failed ejects nothing and arms no timer.
+        if self._fsm_state not in ("starting", "running"):
+            return False
+        ejected = self.p_od_ejected
+        refused = not self._od_usable_without(key)
+        if not refused and reason != "manual":
+            share = (len(ejected) + 1) * 100.0 / len(self.p_keys)
+            refused = share > self.p_od["maxEjectionPercent"]
+        if refused:
+            if reason != "manual":
+                # the counter is an alarm about failing backends that
+                # had to stay; an operator's refused request is not one
+                self._incr_counter("ejection-refused")
+            self.p_log.info('not ejecting backend "%s" (%s): too few '
+                            'backends would be left', key, reason)
+            return False
+
+        now = self._loop.time()
+        rec = self._od_record(key)
+        n = self._od_ejections(key, rec, now) + 1
+        rec["ejections"] = n
+        if ms is None:
+            od = self.p_od
+            ms = min(od["baseEjectionTime"] * 2.0 ** (n - 1),
+                     od["maxEjectionTime"])
+        ent: Dict[str, Any] = {"reason": reason, "at": now,
+                               "until": now + ms / 1000.0,
+                               "durationMs": ms}
+        ent["timer"] = self._loop.call_at(
+            ent["until"], self._od_expired, key, ent)
+        ejected[key] = ent
+        self.p_log.warn('ejecting backend "%s" (%s) for %d ms',
+                        key, reason, ms)
+        self._incr_counter("backend-ejected")
+        # Every slot goes, a monitor included, and not at maxChurnRate's
+        # pace: idle ones stop now, claimed ones when released.
+        for fsm in list(self.p_connections.get(key, ())):
+            fsm.set_unwanted()
+        self.rebalance()
+        self.emit("backendEjected", key, {
+            "reason": reason, "durationMs": ms, "ejections": n})
+        return True
+
+    def _od_expired(self, key: str, ent: Dict[str, Any]) -> None:
+        if self.p_od_ejected.get(key) is ent and \
+                self._fsm_state in ("starting", "running", "failed"):
+            self._od_reinstate(key, "expired")
+
+    def _od_reinstate(self, key: str, reason: str) -> None:
+        ent = self.p_od_ejected.pop(key)
+        ent["timer"].cancel()
+        now = self._loop.time()
+        rec = self._od_record(key)
+        rec["streak"] = 0
+        rec["cleanAt"] = now + ent["durationMs"] / 1000.0
+        self.p_log.info('reinstating backend "%s" (%s)', key, reason)
+        self._incr_counter("backend-reinstated")
+        self.rebalance()
+        self.emit("backendReinstated", key, reason)
+
+    def _od_panic_check(self) -> None:
+        """A backend was just declared dead, or removed by the
+        resolver.  If that leaves none that is neither dead nor
+        ejected, a suspect backend is better than none: lift every
+        ejection."""
+        ejected = self.p_od_ejected
+        for k in self.p_keys:
+            if k not in ejected and k not in self.p_dead:
+                return
+        for k in list(ejected):
+            self._od_reinstate(k, "panic")
+
+    def eject_backend(self, key: str, ms: Optional[float] = None) -> bool:
+        """Eject backend `key` by hand for `ms` milliseconds (default:
+        what outlier detection would give it next; required on a pool
+        without ``outlierDetection``).  ``maxEjectionPercent`` does not
+        apply.  False for an unknown or already ejected key, for the
+        last usable backend, and for a pool that is not starting or
+        running."""
+        if ms is None:
+            if self.p_od is None:
+                raise ValueError("eject_backend() needs ms on a pool "
+                                 "without outlierDetection")
+        elif not mod_utils._num(ms):
+            raise TypeError("ms must be a number")
+        elif not math.isfinite(ms) or ms <= 0:
+            raise ValueError("ms must be finite and > 0")
+        if self._fsm_state not in ("starting", "running"):
+            return False
+        if key not in self.p_backends:
+            return False
+        self._od_init()
+        if key in self.p_od_ejected:
+            return False
+        return self._od_eject(key, "manual", ms)
+
+    def reinstate_backend(self, key: str) -> bool:
+        """End the ejection of backend `key` now; False when it is not
+        ejected."""
+        if not self.p_od_ejected or key not in self.p_od_ejected:
+            return False
+        self._od_reinstate(key, "manual")
+        return True
+
+    def get_outlier_stats(self) -> Dict[str, Any]:
+        """``{"enabled", "ejected": n, "backends": {key:
+        {"consecutiveFailures", "failures", "successes", "ejected",
+        "ejections", "ejectedForMs", "reinstatesInMs"}}}``, one entry
+        per backend the pool knows; ``ejections`` counts consecutive
+        ejections, and the two times are None for a backend that is not
+        ejected."""
+        now = self._loop.time()
+        ejected = self.p_od_ejected or {}
+        recs = self.p_od_backends or {}
+        out: Dict[str, Any] = {}
+        for k in self.p_keys:
+            rec = recs.get(k)
+            ent = ejected.get(k)
+            out[k] = {
+                "consecutiveFailures": rec["streak"] if rec else 0,
+                "failures": rec["failures"] if rec else 0,
+                "successes": rec["successes"] if rec else 0,
+                "ejected": ent is not None,
+                "ejections":
+                    self._od_ejections(k, rec, now) if rec else 0,
+                "ejectedForMs":
+                    None if ent is None else (now - ent["at"]) * 1000.0,
+                "reinstatesInMs": None if ent is None else
+                    max(0.0, (ent["until"] - now) * 1000.0),
+            }
+        return {"enabled": self.p_od is not None,
+                "ejected": len(ejected), "backends": out}
+
     # -- slot lifecycle ----------------------------------------------------
     def add_connection(self, key: str) -> None:
         if self.is_in_state("stopping") or self.is_in_state("stopped"):
@@ -1102,6 +1436,8 @@ class ConnectionPool(FSM):
                    functools.partial(self._slot_state_changed, fsm, key))
         if self.p_age_slots is not None:
             self._age_watch(fsm)
+        if self.p_od is not None:
+            self._od_watch(fsm, key)
         fsm.start()
 
     def _slot_state_changed(self, fsm: ConnectionSlotFSM, key: str,
@@ -1157,6 +1493,9 @@ class ConnectionPool(FSM):
         elif new_state == "failed":
             if key in self.p_backends:
                 self.p_dead[key] = True
+                if self.p_od_ejected:
+                    # before closedBackend weighs the 'failed' state
+                    self._od_panic_check()
             err = fsm.get_socket_mgr().get_last_error()
             if err is not None:
                 self.p_last_error = err

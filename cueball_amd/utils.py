@@ -232,6 +232,75 @@ def assert_connection_age(options: Mapping[str, Any]) -> tuple:
     return (age, 0.2 if spread is None else spread)
 
 
+_OUTLIER_KEYS = ("consecutiveFailures", "baseEjectionTime",
+                 "maxEjectionTime", "maxEjectionPercent", "countClose",
+                 "countSocketClose")
+
+
+def assert_outlier_detection(options: Mapping[str, Any],
+                             count_default: bool = True
+                             ) -> Optional[Dict[str, Any]]:
+    """Validate ``outlierDetection`` and return it with every default
+    filled in, or None when the option is off.  ``count_default`` is the
+    default of ``countClose`` and ``countSocketClose``: True for a pool,
+    False for the pools of an agent, which closes leases on purpose."""
+    od = options.get("outlierDetection")
+    if od is None:
+        return None
+    name = "options.outlierDetection"
+    if not isinstance(od, Mapping):
+        raise TypeError("%s must be a mapping" % name)
+    extra = set(od.keys()) - set(_OUTLIER_KEYS)
+    if extra:
+        raise ValueError("%s has unknown keys: %r"
+                         % (name, sorted(extra, key=str)))
+
+    fails = od.get("consecutiveFailures")
+    if fails is None:
+        fails = 5
+    if not isinstance(fails, int) or isinstance(fails, bool):
+        raise TypeError("%s.consecutiveFailures must be an int" % name)
+    if fails < 1:
+        raise ValueError("%s.consecutiveFailures must be >= 1" % name)
+
+    base = od.get("baseEjectionTime")
+    if base is None:
+        base = 30000
+    if not _num(base):
+        raise TypeError("%s.baseEjectionTime must be a number" % name)
+    if not math.isfinite(base) or base <= 0:
+        raise ValueError("%s.baseEjectionTime must be finite and > 0" % name)
+
+    longest = od.get("maxEjectionTime")
+    if longest is None:
+        longest = max(300000, base)
+    if not _num(longest):
+        raise TypeError("%s.maxEjectionTime must be a number" % name)
+    if not math.isfinite(longest) or longest < base:
+        raise ValueError("%s.maxEjectionTime must be finite and >= "
+                         "baseEjectionTime" % name)
+
+    percent = od.get("maxEjectionPercent")
+    if percent is None:
+        percent = 50
+    if not _num(percent):
+        raise TypeError("%s.maxEjectionPercent must be a number" % name)
+    if not (0 < percent <= 100):
+        raise ValueError("%s.maxEjectionPercent must be in (0, 100]" % name)
+
+    out: Dict[str, Any] = {
+        "consecutiveFailures": fails, "baseEjectionTime": base,
+        "maxEjectionTime": longest, "maxEjectionPercent": percent}
+    for k in ("countClose", "countSocketClose"):
+        v = od.get(k)
+        if v is None:
+            v = count_default
+        if not isinstance(v, bool):
+            raise TypeError("%s.%s must be a bool" % (name, k))
+        out[k] = v
+    return out
+
+
 def plan_rebalance(connections: Mapping[str, Sequence[Any]],
                    dead: Mapping[str, bool],
                    target: int, maximum: int,
