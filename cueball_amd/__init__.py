@@ -14,7 +14,8 @@ from .connection_fsm import ClaimHandle, ConnectionSlotFSM
 from .errors import (ClaimHandleMisusedError, ClaimTimeoutError,
                      ConnectionClosedError, ConnectionError_,
                      ConnectionTimeoutError, CueballError, NoBackendsError,
-                     PoolFailedError, PoolStoppingError)
+                     PoolFailedError, PoolStoppingError,
+                     RequestTimeoutError)
 from .events import EventEmitter
 from .fsm import FSM, FSMError
 from .kang import KangServer
@@ -59,6 +60,7 @@ __all__ = [
     "NoBackendsError",
     "PoolFailedError",
     "PoolStoppingError",
+    "RequestTimeoutError",
     "ConnectionError_",
     "ConnectionTimeoutError",
     "ConnectionClosedError",

@@ -12,6 +12,10 @@ machinery (cueball_amd.http_client):
   leak check + release (benefit of the doubt), req 'abort' => cancel or
   close, 'agentRemove' => hold until close (lib/agent.js:275-396).
 - ``request(...)``/``request_async(...)`` — convenience wrappers.
+- the opt-in ``retry`` option routes ``request()``/``request_async()``
+  through a retry driver (cueball_amd.retry): per-try and total
+  timeouts, retries on another backend, a retry budget per host.
+  ``add_request()`` with a caller-built request never retries.
 - ping checker: claims the exact idle socket and runs GET <ping>; a 5xx
   or error closes the connection, anything else releases it
   (lib/agent.js:398-455, PingAgent :530-569).
@@ -20,8 +24,9 @@ machinery (cueball_amd.http_client):
 from __future__ import annotations
 
 import ssl as mod_ssl
-from typing import Any, Callable, Dict, Optional
+from typing import Any, Callable, Dict, Mapping, Optional
 
+from . import retry as mod_retry
 from . import utils as mod_utils
 from .connection import TcpConnection
 from .errors import CueballError
@@ -54,6 +59,16 @@ class FakeSocket(EventEmitter):
 
 
 class Agent(EventEmitter):
+    # The retry option's state.  Class-level defaults, so that an agent
+    # without the option carries no extra instance attribute.
+    #: the validated ``retry`` option, defaults filled in
+    cba_retry: Optional[Dict[str, Any]] = None
+    #: the same as the driver reads it (retry.RetryPolicy)
+    cba_retry_policy: Any = None
+    #: host -> retry.RetryHost: budget, counters, pending backoffs
+    cba_retry_hosts: Optional[Dict[str, Any]] = None
+    _retry_metrics: Optional[tuple] = None
+
     def __init__(self, options: Dict[str, Any]) -> None:
         super().__init__()
         if not isinstance(options.get("defaultPort"), int):
@@ -112,6 +127,15 @@ class Agent(EventEmitter):
         # socket error under a request and a failed ping.
         self.cba_outlier = mod_utils.assert_outlier_detection(
             options, count_default=False)
+
+        # Request retries (opt-in): see the "retries" section below.
+        # Off means not one attribute is set here.
+        retry = mod_utils.assert_retry_policy(options)
+        if retry is not None:
+            self.cba_retry = retry
+            self.cba_retry_policy = mod_retry.RetryPolicy(retry)
+            self.cba_retry_hosts = {}
+            self._register_retry_metrics()
 
         for host in options.get("initialDomains") or ():
             self._add_pool(host, {})
@@ -293,6 +317,13 @@ class Agent(EventEmitter):
                                "already stopped")
         self.cba_stopped = True
         self.log.debug("CueBallAgent stopping all pools")
+        if self.cba_retry_hosts:
+            # a request between two tries holds nothing a pool could
+            # fail: end it here
+            err = CueballError("CueBallAgent is stopped and cannot handle "
+                               "new requests")
+            for rhost in self.cba_retry_hosts.values():
+                rhost.stop(err)
         hosts = list(self.pools.keys())
         remaining = {"n": len(hosts)}
 
@@ -355,18 +386,34 @@ class Agent(EventEmitter):
         if host not in self.pools:
             self._add_pool(host, options)
         pool = self.pools[host]
-        _RequestTicket(self, pool, req)
+        if self.cba_retry is not None and isinstance(req, _TryRequest):
+            _TryTicket(self, pool, req)
+        else:
+            _RequestTicket(self, pool, req)
 
     def request(self, options_or_host: Any, method: str = "GET",
                 path: str = "/", headers: Optional[Dict[str, str]] = None,
                 body: Optional[bytes] = None,
-                cb: Optional[Callable] = None) -> HttpRequest:
+                cb: Optional[Callable] = None,
+                retry: Any = None) -> Any:
         """Convenience: run one request; cb(err, response) after the
-        body has fully arrived."""
+        body has fully arrived.
+
+        On an agent with the ``retry`` option the request runs under
+        the retry driver and a ``retry.RetriedRequest`` is returned;
+        ``retry=False`` switches the driver off for this call, a
+        mapping overrides keys of the agent's policy (all but
+        ``budget``) for this call."""
         if isinstance(options_or_host, str):
             host = options_or_host
         else:
             host = options_or_host.get("host")
+        if retry is not None or self.cba_retry is not None:
+            policy = self._retry_policy_for(retry)
+            if policy is not None:
+                return self._request_retried(
+                    policy, options_or_host, host, method, path, headers,
+                    body, cb)
         req = HttpRequest(method, path, headers=headers, body=body,
                           host=host)
 
@@ -385,7 +432,8 @@ class Agent(EventEmitter):
     async def request_async(self, options_or_host: Any, method: str = "GET",
                             path: str = "/",
                             headers: Optional[Dict[str, str]] = None,
-                            body: Optional[bytes] = None) -> HttpResponse:
+                            body: Optional[bytes] = None,
+                            retry: Any = None) -> HttpResponse:
         fut = self._loop.create_future()
 
         def cb(err: Optional[BaseException],
@@ -397,8 +445,105 @@ class Agent(EventEmitter):
             else:
                 fut.set_result(resp)
 
-        self.request(options_or_host, method, path, headers, body, cb)
+        if retry is None:
+            self.request(options_or_host, method, path, headers, body, cb)
+        else:
+            self.request(options_or_host, method, path, headers, body, cb,
+                         retry=retry)
         return await fut
+
+    # -- retries --------------------------------------------------------------
+    #
+    # With the ``retry`` option, request() hands the request to a
+    # retry.RetriedRequest.  Each try is a fresh HttpRequest that goes
+    # through add_request() like any other; it is a _TryRequest, so
+    # that its ticket (_TryTicket) can pass the backends to avoid to the
+    # claim and note which backend the try was served by.
+
+    _RETRY_METRICS = (
+        ("cueball_agent_retries_total",
+         "Requests retried by the agent, by host and reason"),
+        ("cueball_agent_retry_budget_exhausted_total",
+         "Retries the agent's retry budget denied, by host"),
+        ("cueball_agent_request_timeouts_total",
+         "Per-try and total request timeouts that fired, by host"),
+    )
+
+    def _register_retry_metrics(self) -> None:
+        try:
+            self._retry_metrics = tuple(
+                self.collector.counter(name=name, help=help_)
+                for name, help_ in self._RETRY_METRICS)
+        except (AttributeError, ValueError, TypeError):
+            self._retry_metrics = None  # foreign collector
+
+    def _retry_counted(self, host: str, counter: str) -> None:
+        metrics = self._retry_metrics
+        if metrics is None:
+            return
+        if counter == "retry-budget-exhausted":
+            metrics[1].increment({"host": host})
+        elif counter.startswith("retry-"):
+            metrics[0].increment({"host": host, "reason": counter[6:]})
+        elif counter.startswith("timeout-"):
+            metrics[2].increment({"host": host, "kind": counter[8:]})
+
+    def _retry_policy_for(self, retry: Any) -> Any:
+        """The policy of one call, None for a call without the driver."""
+        if retry is None:
+            return self.cba_retry_policy
+        if retry is False:
+            return None
+        if self.cba_retry is None:
+            if isinstance(retry, Mapping):
+                raise ValueError("retry= needs an agent that was created "
+                                 "with options.retry")
+            raise TypeError("retry= must be False or a mapping")
+        return mod_retry.RetryPolicy(
+            mod_utils.override_retry_policy(self.cba_retry, retry))
+
+    def _request_retried(self, policy: Any, options_or_host: Any,
+                         host: Any, method: str, path: str,
+                         headers: Optional[Dict[str, str]],
+                         body: Optional[bytes],
+                         cb: Optional[Callable]) -> Any:
+        if not isinstance(host, str):
+            if isinstance(options_or_host, Mapping):
+                host = options_or_host.get("hostname")
+            if not isinstance(host, str):
+                raise TypeError("hostname is required")
+        rhost = self.cba_retry_hosts.get(host)
+        if rhost is None:
+            rhost = self.cba_retry_hosts[host] = mod_retry.RetryHost(
+                host, self.cba_retry["budget"], self._retry_counted)
+
+        def start_try(avoid: tuple) -> HttpRequest:
+            req = _TryRequest(method, path, headers=headers, body=body,
+                              host=host)
+            if avoid:
+                req.try_avoid = avoid
+            self.add_request(req, options_or_host)
+            return req
+
+        rreq = mod_retry.RetriedRequest(self._loop, policy, rhost, method,
+                                        start_try, self.is_stopped)
+        if cb is not None:
+            def on_resp(resp: HttpResponse) -> None:
+                if resp.complete:
+                    cb(None, resp)
+                else:
+                    resp.on("end", lambda: cb(None, resp))
+
+            rreq.on("response", on_resp)
+            rreq.on("error", lambda e: cb(e, None))
+        return rreq.start()
+
+    def get_retry_stats(self) -> Dict[str, Any]:
+        """Per host that has seen a request: ``{"active", "retrying",
+        "limit", "counters": {...}}``; ``limit`` is None without a
+        budget.  Empty on an agent without ``retry``."""
+        return {host: rhost.stats()
+                for host, rhost in (self.cba_retry_hosts or {}).items()}
 
     # -- health checking -----------------------------------------------------
     def _check_socket(self, host: str, handle: Any, socket: Any) -> None:
@@ -508,6 +653,49 @@ class _RequestTicket:
         # the lease until 'close'.
         self.sock.remove_listener("free", self.on_free)
         self.req.remove_listener("abort", self.on_abort)
+
+
+class _TryRequest(HttpRequest):
+    """One try of a retried request (see Agent._request_retried)."""
+
+    #: backend keys the try's claim is to avoid
+    try_avoid: tuple = ()
+    #: the try's claim handle and its slot, None until claimed
+    try_handle: Any = None
+    try_slot: Any = None
+
+    @property
+    def try_backend(self) -> Optional[str]:
+        """The key of the backend the try was claimed on, None until
+        then.  Looked up only when a try has failed."""
+        slot = self.try_slot
+        return None if slot is None else slot.get_backend().get("key")
+
+
+class _TryTicket(_RequestTicket):
+    """A _TryRequest's ticket: the claim avoids the backends the
+    request has failed on, and the try learns where it landed."""
+
+    __slots__ = ()
+
+    def __init__(self, agent: "Agent", pool: Any, req: _TryRequest) -> None:
+        self.agent = agent
+        self.req = req
+        self.conn = None
+        self.sock = None
+        req.once("abort", self.on_abort)
+        options: Dict[str, Any] = {"errorOnEmpty": agent.cba_err_on_empty}
+        if req.try_avoid:
+            options["avoidBackends"] = req.try_avoid
+        self.waiter = pool.claim(options, self.claimed)
+
+    def claimed(self, err: Optional[BaseException], connh: Any = None,
+                socket: Any = None) -> None:
+        if err is None:
+            req = self.req
+            req.try_handle = connh
+            req.try_slot = connh.ch_slot
+        _RequestTicket.claimed(self, err, connh, socket)
 
 
 class PingAgent(EventEmitter):

@@ -335,6 +335,17 @@ def _report_failure(handle: Any, err: Optional[BaseException]) -> None:
         handle.ch_log.debug("claimer reported the lease as failed: %r", err)
 
 
+def _handle_backend(handle: Any) -> Optional[Dict[str, Any]]:
+    """ClaimHandle.get_backend(), shared by both claim handles: the
+    backend dict of the slot the handle holds a lease on, None when it
+    holds none (not claimed yet, or released, closed, cancelled or
+    failed since)."""
+    slot = handle.ch_slot
+    if slot is None or handle._fsm_state != "claimed":
+        return None
+    return slot.get_backend()
+
+
 class ClaimHandle(FSM):
     """Handle given to pool users; drives the claim double-handshake.
 
@@ -503,6 +514,9 @@ class ClaimHandle(FSM):
 
     def report_failure(self, err: Optional[BaseException] = None) -> None:
         _report_failure(self, err)
+
+    def get_backend(self) -> Optional[Dict[str, Any]]:
+        return _handle_backend(self)
 
     # -- states ----------------------------------------------------------
     def state_waiting(self, S: StateScope) -> None:
@@ -675,6 +689,9 @@ if _native_count is not None:
         def report_failure(self,
                            err: Optional[BaseException] = None) -> None:
             _report_failure(self, err)
+
+        def get_backend(self) -> Optional[Dict[str, Any]]:
+            return _handle_backend(self)
 
 
 def count_listeners(emitter: Any, event: str) -> int:

@@ -16,6 +16,7 @@ __all__ = [
     "NoBackendsError",
     "PoolFailedError",
     "PoolStoppingError",
+    "RequestTimeoutError",
     "ConnectionError_",
     "ConnectionTimeoutError",
     "ConnectionClosedError",
@@ -107,6 +108,20 @@ class PoolStoppingError(CueballError):
             "Pool %s (%s) is stopping and cannot take new requests"
             % (uuid, getattr(pool, "p_domain", "?"))
         )
+
+
+class RequestTimeoutError(CueballError):
+    """An agent's ``retry`` option ran out of time: ``kind`` is
+    "per-try" (``perTryTimeout``, one try) or "total" (``totalTimeout``,
+    the whole request); ``timeout_ms`` the limit that fired."""
+
+    def __init__(self, kind: str, timeout_ms: float) -> None:
+        self.kind = kind
+        self.timeout_ms = timeout_ms
+        what = "A try of the request" if kind == "per-try" \
+            else "The request"
+        super().__init__("%s timed out after %g ms (%s timeout)"
+                         % (what, timeout_ms, kind))
 
 
 class ConnectionError_(CueballError):

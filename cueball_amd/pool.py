@@ -21,7 +21,7 @@ import os as _os
 import random
 import time as mod_time
 import uuid as mod_uuid
-from typing import Any, Callable, Dict, List, Optional
+from typing import Any, Callable, Dict, List, Mapping, Optional
 
 from . import codel as mod_codel
 from . import errors as mod_errors
@@ -107,6 +107,34 @@ class _ClaimTicket:
     def __call__(self, st: str) -> None:
         if st == "waiting":
             self.pool._ticket_slow(self.handle, self.err_on_empty)
+
+
+class _AvoidClaimTicket:
+    """The ticket of a claim that carries ``avoidBackends``: always the
+    Python slow path, with the set handed along, on either runtime.  It
+    unregisters itself when the handle settles (the native handle's
+    terminal cleanup knows only its own ticket type)."""
+
+    __slots__ = ("pool", "handle", "err_on_empty", "avoid")
+
+    _cueball_ticket = True
+
+    def __init__(self, pool: "ConnectionPool", handle: ClaimHandle,
+                 err_on_empty: bool, avoid: frozenset) -> None:
+        self.pool = pool
+        self.handle = handle
+        self.err_on_empty = err_on_empty
+        self.avoid = avoid
+
+    def __call__(self, st: str) -> None:
+        handle = self.handle
+        if handle is None:
+            return
+        if st == "waiting":
+            self.pool._ticket_slow(handle, self.err_on_empty, self.avoid)
+        elif st in ("released", "closed", "cancelled", "failed"):
+            self.handle = None
+            handle.remove_listener("stateChanged", self)
 
 
 _NativeClaimTicket = None
@@ -1547,8 +1575,35 @@ class ConnectionPool(FSM):
             "waiterCount": len(self.p_waiters),
         }
 
-    def _ticket_slow(self, handle: ClaimHandle,
-                     err_on_empty: bool) -> None:
+    def _idle_avoiding(self, avoid: frozenset) -> Optional[ConnectionSlotFSM]:
+        """Unlink and return the first idle slot, in queue order, whose
+        backend is not in `avoid`; the first idle slot of all when every
+        one is; None when nothing is idle.  Stale entries ahead of the
+        slot that decides the walk are unlinked, as in _ticket_slow;
+        idle slots that are passed over stay linked where they are."""
+        found: List[Any] = [None, None]     # [first idle, match]
+
+        def visit(fsm: ConnectionSlotFSM, node: Any) -> None:
+            if found[1] is not None:
+                return
+            if not fsm.is_in_state("idle"):
+                node.remove()
+                fsm.p_idleq_node = None
+                return
+            if fsm.csf_backend.get("key") not in avoid:
+                found[1] = fsm
+            elif found[0] is None:
+                found[0] = fsm
+
+        self.p_idleq.for_each(visit)
+        fsm = found[1] if found[1] is not None else found[0]
+        if fsm is not None:
+            fsm.p_idleq_node.remove()
+            fsm.p_idleq_node = None
+        return fsm
+
+    def _ticket_slow(self, handle: ClaimHandle, err_on_empty: bool,
+                     avoid: Optional[frozenset] = None) -> None:
         """The full claim-retry logic (lib/pool.js:922-968): invoked on
         every handle return to 'waiting' — directly in pure mode, and
         as the native ClaimTicket's off-hot-path fallback (pool not in
@@ -1570,6 +1625,14 @@ class ConnectionPool(FSM):
         # stale ('stateChanged' is async): just unlink and skip them;
         # the slot dispatcher copes (lib/pool.js:934-951).
         idleq = self.p_idleq
+        if avoid is not None:
+            # a soft preference among the idle slots, nothing more:
+            # from here on the claim is like any other
+            fsm = self._idle_avoiding(avoid)
+            if fsm is not None:
+                handle.try_(fsm)
+                self._note_demand()
+                return
         while idleq._len > 0:
             fsm = idleq.shift()
             fsm.p_idleq_node = None
@@ -1601,6 +1664,11 @@ class ConnectionPool(FSM):
 
         Returns the ClaimHandle (or a cancel-only stub when the pool is
         stopping/failed, lib/pool.js:889-910).
+
+        Options: ``timeout`` (ms), ``errorOnEmpty``, and
+        ``avoidBackends``, an iterable of backend keys: among the idle
+        slots the claim prefers one on another backend.  Only a
+        preference: it never makes the claim wait, fail or time out.
         """
         # fast path: claim({}, cb) / claim(cb) with no CoDel — the
         # overwhelmingly common call shape on the hot path
@@ -1621,6 +1689,7 @@ class ConnectionPool(FSM):
                     cb, mod_errors.PoolStoppingError(self))
             err_on_empty = False
             timeout = math.inf
+            avoid = None
         else:
             if callable(options) and cb is None:
                 cb = options
@@ -1629,6 +1698,9 @@ class ConnectionPool(FSM):
             if cb is None:
                 raise TypeError("claim() requires a callback")
             err_on_empty = bool(options.get("errorOnEmpty", False))
+            avoid = options.get("avoidBackends")
+            if avoid is not None:
+                avoid = self._assert_avoid(avoid)
 
             if self.p_codel is not None:
                 if options.get("timeout") is not None:
@@ -1657,6 +1729,12 @@ class ConnectionPool(FSM):
         # stateChanged('waiting'); the ticket receives it on the next
         # loop turn and runs the first try_next then — claim() never
         # fires the callback synchronously (lib/pool.js:922-968).
+        if avoid is not None:
+            handle = ClaimHandle.fast(self, stack, cb, self.p_claim_log,
+                                      timeout, self._loop)
+            handle.on("stateChanged",
+                      _AvoidClaimTicket(self, handle, err_on_empty, avoid))
+            return handle
         if _native_claim_fast is not None:
             return _native_claim_fast(ClaimHandle, self, stack, cb,
                                       self.p_claim_log, timeout,
@@ -1665,6 +1743,25 @@ class ConnectionPool(FSM):
                                   timeout, self._loop)
         handle.on("stateChanged", _ClaimTicket(self, handle, err_on_empty))
         return handle
+
+    def _assert_avoid(self, avoid: Any) -> Optional[frozenset]:
+        """``avoidBackends``: an iterable of backend keys.  Returns the
+        keys this pool knows, or None when that leaves nothing to
+        avoid."""
+        if isinstance(avoid, (str, bytes)) or isinstance(avoid, Mapping):
+            raise TypeError("options.avoidBackends must be an iterable of "
+                            "backend keys")
+        try:
+            keys = list(avoid)
+        except TypeError:
+            raise TypeError("options.avoidBackends must be an iterable of "
+                            "backend keys")
+        for k in keys:
+            if not isinstance(k, str):
+                raise TypeError("options.avoidBackends must hold backend "
+                                "keys (strings)")
+        known = frozenset(k for k in keys if k in self.p_backends)
+        return known or None
 
     def _claim_shortcircuit(self, cb: Callable, err: BaseException):
         state = {"done": False}

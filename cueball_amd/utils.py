@@ -301,6 +301,178 @@ def assert_outlier_detection(options: Mapping[str, Any],
     return out
 
 
+RETRY_REASONS = ("reset", "timeout", "status", "claim-failure")
+
+_RETRY_KEYS = ("maxRetries", "retryOn", "retryStatuses", "methods",
+               "perTryTimeout", "totalTimeout", "delay", "maxDelay",
+               "jitter", "avoidFailedBackends", "budget")
+_RETRY_BUDGET_KEYS = ("percent", "minConcurrency")
+
+
+def _retry_list(value: Any, name: str, default: Sequence[Any]) -> List[Any]:
+    """A list option: any iterable but a string or a mapping, without
+    duplicates, in the order given."""
+    if value is None:
+        return list(default)
+    if isinstance(value, (str, bytes, Mapping)):
+        raise TypeError("%s must be a list" % name)
+    try:
+        items = list(value)
+    except TypeError:
+        raise TypeError("%s must be a list" % name)
+    out: List[Any] = []
+    for item in items:
+        if item not in out:
+            out.append(item)
+    return out
+
+
+def _retry_ms(value: Any, name: str) -> Optional[float]:
+    if value is None:
+        return None
+    if not _num(value):
+        raise TypeError("%s must be a number" % name)
+    if not math.isfinite(value) or value <= 0:
+        raise ValueError("%s must be finite and > 0" % name)
+    return value
+
+
+def assert_retry_policy(options: Mapping[str, Any]
+                        ) -> Optional[Dict[str, Any]]:
+    """Validate an agent's ``retry`` option and return the policy with
+    every default filled in, or None when the option is off.  ``budget``
+    is a mapping ``{percent, minConcurrency}``; an explicit None turns
+    the budget off."""
+    retry = options.get("retry")
+    if retry is None:
+        return None
+    name = "options.retry"
+    if not isinstance(retry, Mapping):
+        raise TypeError("%s must be a mapping" % name)
+    extra = set(retry.keys()) - set(_RETRY_KEYS)
+    if extra:
+        raise ValueError("%s has unknown keys: %r"
+                         % (name, sorted(extra, key=str)))
+
+    retries = retry.get("maxRetries")
+    if retries is None:
+        retries = 2
+    if not isinstance(retries, int) or isinstance(retries, bool):
+        raise TypeError("%s.maxRetries must be an int" % name)
+    if retries < 0:
+        raise ValueError("%s.maxRetries must be >= 0" % name)
+
+    retry_on = _retry_list(retry.get("retryOn"), name + ".retryOn",
+                           ("reset", "timeout"))
+    for reason in retry_on:
+        if not isinstance(reason, str):
+            raise TypeError("%s.retryOn must hold strings" % name)
+        if reason not in RETRY_REASONS:
+            raise ValueError("%s.retryOn: unknown reason %r (one of %s)"
+                             % (name, reason, ", ".join(RETRY_REASONS)))
+
+    statuses = _retry_list(retry.get("retryStatuses"),
+                           name + ".retryStatuses", (502, 503, 504))
+    for code in statuses:
+        if not isinstance(code, int) or isinstance(code, bool):
+            raise TypeError("%s.retryStatuses must hold ints" % name)
+        if not (100 <= code <= 599):
+            raise ValueError("%s.retryStatuses: %d is not an HTTP status"
+                             % (name, code))
+
+    methods = _retry_list(retry.get("methods"), name + ".methods",
+                          ("GET", "HEAD", "OPTIONS", "PUT", "DELETE"))
+    for method in methods:
+        if not isinstance(method, str):
+            raise TypeError("%s.methods must hold strings" % name)
+        if not method:
+            raise ValueError("%s.methods must not hold an empty string"
+                             % name)
+    methods = _retry_list([m.upper() for m in methods], "", ())
+
+    per_try = _retry_ms(retry.get("perTryTimeout"), name + ".perTryTimeout")
+    total = _retry_ms(retry.get("totalTimeout"), name + ".totalTimeout")
+
+    delay = retry.get("delay")
+    if delay is None:
+        delay = 25
+    if not _num(delay):
+        raise TypeError("%s.delay must be a number" % name)
+    if not math.isfinite(delay) or delay < 0:
+        raise ValueError("%s.delay must be finite and >= 0" % name)
+    max_delay = retry.get("maxDelay")
+    if max_delay is None:
+        max_delay = max(250, delay)
+    if not _num(max_delay):
+        raise TypeError("%s.maxDelay must be a number" % name)
+    if not math.isfinite(max_delay) or max_delay < delay:
+        raise ValueError("%s.maxDelay must be finite and >= delay" % name)
+
+    out: Dict[str, Any] = {
+        "maxRetries": retries, "retryOn": retry_on,
+        "retryStatuses": statuses, "methods": methods,
+        "perTryTimeout": per_try, "totalTimeout": total,
+        "delay": delay, "maxDelay": max_delay}
+    for k in ("jitter", "avoidFailedBackends"):
+        v = retry.get(k)
+        if v is None:
+            v = True
+        if not isinstance(v, bool):
+            raise TypeError("%s.%s must be a bool" % (name, k))
+        out[k] = v
+
+    if "budget" in retry and retry["budget"] is None:
+        out["budget"] = None
+        return out
+    budget = retry.get("budget")
+    if budget is None:
+        budget = {}
+    bname = name + ".budget"
+    if not isinstance(budget, Mapping):
+        raise TypeError("%s must be a mapping or None" % bname)
+    extra = set(budget.keys()) - set(_RETRY_BUDGET_KEYS)
+    if extra:
+        raise ValueError("%s has unknown keys: %r"
+                         % (bname, sorted(extra, key=str)))
+    percent = budget.get("percent")
+    if percent is None:
+        percent = 20
+    if not _num(percent):
+        raise TypeError("%s.percent must be a number" % bname)
+    if not (0 <= percent <= 100):
+        raise ValueError("%s.percent must be in [0, 100]" % bname)
+    min_conc = budget.get("minConcurrency")
+    if min_conc is None:
+        min_conc = 3
+    if not isinstance(min_conc, int) or isinstance(min_conc, bool):
+        raise TypeError("%s.minConcurrency must be an int" % bname)
+    if min_conc < 0:
+        raise ValueError("%s.minConcurrency must be >= 0" % bname)
+    out["budget"] = {"percent": percent, "minConcurrency": min_conc}
+    return out
+
+
+def override_retry_policy(policy: Optional[Mapping[str, Any]],
+                          override: Any) -> Dict[str, Any]:
+    """The policy of one call: `policy` (an agent's validated ``retry``)
+    with the keys of `override` replaced and validated again.  Every
+    key but ``budget`` may be overridden: the budget is shared by all
+    requests to a host."""
+    if policy is None:
+        raise ValueError("retry= needs an agent that was created with "
+                         "options.retry")
+    if not isinstance(override, Mapping):
+        raise TypeError("retry= must be False or a mapping")
+    if "budget" in override:
+        raise ValueError("retry= cannot override budget: it is shared by "
+                         "every request to the host")
+    merged = dict(policy)
+    merged.update(override)
+    out = assert_retry_policy({"retry": merged})
+    assert out is not None
+    return out
+
+
 def plan_rebalance(connections: Mapping[str, Sequence[Any]],
                    dead: Mapping[str, bool],
                    target: int, maximum: int,
