@@ -14,6 +14,7 @@ draining -> stopped (state diagram at lib/set.js:632-675).
 
 from __future__ import annotations
 
+import functools
 import math
 import random
 import time as mod_time
@@ -35,6 +36,21 @@ class ConnectionSet(FSM):
     # with srvRanking on (as in ConnectionPool)
     cs_ranks: Optional[Dict[str, tuple]] = None
     cs_active_priority: Optional[int] = None
+
+    # Connection age / recycle() state, class-level for the same
+    # reason: a set without maxConnectionAge that never called
+    # recycle() has none of these in its instance dict.
+    cs_age_max: Optional[float] = None      # maxConnectionAge, ms
+    cs_age_spread: Optional[float] = None
+    # slot -> [deadline (loop time), "age" | "manual"]; None when off
+    cs_age_slots: Optional[Dict[Any, list]] = None
+    # the one replacement in flight: {"key", "old", "new", "reason"}
+    cs_age_repl: Optional[Dict[str, Any]] = None
+    # slots no longer (or never) in cs_fsm that are still closing:
+    # swapped-out predecessors and given-up replacements -> backend key
+    cs_age_retired: Optional[Dict[Any, str]] = None
+    cs_age_timer = None
+    cs_age_timer_at: Optional[float] = None
 
     def __init__(self, options: Dict[str, Any]) -> None:
         if not callable(options.get("constructor")):
@@ -99,6 +115,15 @@ class ConnectionSet(FSM):
         if srv_ranking:
             self.cs_ranks = {}
 
+        # Connection age (opt-in): see the "connection age" section
+        # below.  Off means not one attribute is set here.
+        age, spread = mod_utils.assert_connection_age(options)
+        if age is not None:
+            self.cs_age_max = age
+            self.cs_age_spread = spread
+            self.cs_age_slots = {}
+            self.cs_age_retired = {}
+
         super().__init__("starting", loop=loop_opt)
 
         self.cs_rebal_timer = _IntervalTimer(self._loop, 10_000)
@@ -156,6 +181,8 @@ class ConnectionSet(FSM):
             lconn = self.cs_lconns.get(ck)
             if lconn is not None and not lconn.is_in_state("stopped"):
                 lconn.drain()
+        if self.cs_age_repl is not None:
+            self._age_cancel(k)
 
     def is_declared_dead(self, backend: str) -> bool:
         return self.cs_dead.get(backend) is True
@@ -222,6 +249,9 @@ class ConnectionSet(FSM):
         self._subscribe_resolver(S)
         S.on(self.cs_rebal_timer, "timeout", self.rebalance)
         S.on(self.cs_shuffle_timer, "timeout", self.reshuffle)
+        if self.cs_age_slots is not None:
+            # whatever came due while the set was not running
+            S.immediate(self._age_run)
 
         def on_closed_backend(*a: Any) -> None:
             dead = len(self.cs_dead)
@@ -237,6 +267,11 @@ class ConnectionSet(FSM):
         S.valid_transitions(["stopped"])
         self.cs_backends = {}
         fsms = list(self.cs_fsm.values())
+        if self.cs_age_slots is not None:
+            # a replacement in flight and predecessors still closing
+            # are waited for like every other slot
+            self._age_stop()
+            fsms.extend(self.cs_age_retired)
         remaining = {"n": len(fsms)}
 
         def one_done() -> None:
@@ -322,7 +357,8 @@ class ConnectionSet(FSM):
     def get_stats(self) -> Dict[str, Any]:
         return {
             "counters": dict(self.cs_counters),
-            "totalConnections": len(self.cs_fsm),
+            "totalConnections": len(self.cs_fsm) +
+            (0 if self.cs_age_repl is None else 1),
             "connections": len(self.cs_connections),
             "deadBackends": len(self.cs_dead),
         }
@@ -398,6 +434,8 @@ class ConnectionSet(FSM):
             if fsm.is_in_state("busy") or fsm.is_in_state("idle"):
                 working -= 1
             fsm.set_unwanted()
+            if self.cs_age_repl is not None:
+                self._age_cancel(k)
             if fsm.is_in_state("stopped") or fsm.is_in_state("failed"):
                 self.cs_fsm.pop(k, None)
                 total -= 1
@@ -426,8 +464,13 @@ class ConnectionSet(FSM):
                                % event)
         return self.emit(event, *args)
 
-    def create_logi_conn(self, key: str) -> None:
-        fsm = self.cs_fsm[key]
+    def create_logi_conn(self, key: str,
+                         fsm: Optional[ConnectionSlotFSM] = None) -> None:
+        """Open the next serial-numbered LogicalConnection on `fsm`, the
+        slot it serves: ``cs_fsm[key]`` unless told otherwise (with a
+        replacement in flight a backend has two slots)."""
+        if fsm is None:
+            fsm = self.cs_fsm[key]
         if key not in self.cs_serials:
             self.cs_serials[key] = 1
         self.cs_connection_keys.setdefault(key, [])
@@ -448,6 +491,14 @@ class ConnectionSet(FSM):
         self.cs_lconns[ckey] = lconn
 
         def on_lconn_state(st: str) -> None:
+            if st == "advertised":
+                # the successor has been 'added': now, and only now,
+                # its predecessor may go
+                repl = self.cs_age_repl
+                if repl is not None and repl["new"] is fsm and \
+                        lconn.is_in_state("advertised"):
+                    self._age_swap()
+                return
             if st != "stopped":
                 return
             self.cs_lconns.pop(ckey, None)
@@ -460,7 +511,19 @@ class ConnectionSet(FSM):
                 return
             if fsm.is_in_state("failed") or fsm.is_in_state("stopped"):
                 return
-            self.create_logi_conn(key)
+            if not fsm.csf_wanted:
+                # an unwanted slot never offers itself again: a
+                # LogicalConnection chained here would sit in init
+                # for good
+                return
+            repl = self.cs_age_repl
+            if repl is not None and repl["old"] is fsm:
+                # the predecessor went away by itself (socket death or
+                # hdl.close()) before its replacement was up: the
+                # replacement takes over, nothing more is chained here
+                self._age_swap()
+                return
+            self.create_logi_conn(key, fsm)
 
         lconn.on("stateChanged", on_lconn_state)
 
@@ -468,29 +531,41 @@ class ConnectionSet(FSM):
         if self.is_in_state("stopping") or self.is_in_state("stopped"):
             return
 
+        fsm = self._make_slot(key, self.cs_dead.get(key) is True)
+        if key in self.cs_fsm:
+            raise AssertionError("slot for %s already exists" % key)
+        self.cs_fsm[key] = fsm
+        self._start_slot(key, fsm)
+
+    def _make_slot(self, key: str, monitor: bool) -> ConnectionSlotFSM:
         backend = self.cs_backends[key]
         backend["key"] = key
-
-        fsm = ConnectionSlotFSM({
+        return ConnectionSlotFSM({
             "constructor": self.cs_constructor,
             "backend": backend,
             "log": self.cs_log,
             "pool": self,
             "recovery": self.cs_recovery,
-            "monitor": self.cs_dead.get(key) is True,
+            "monitor": monitor,
             "loop": self._loop,
         })
-        if key in self.cs_fsm:
-            raise AssertionError("slot for %s already exists" % key)
-        self.cs_fsm[key] = fsm
 
-        self.create_logi_conn(key)
+    def _start_slot(self, key: str, fsm: ConnectionSlotFSM) -> None:
+        if self.cs_age_slots is not None:
+            self._age_watch(fsm)
+        self.create_logi_conn(key, fsm)
 
         # rebalance when a slot reaches idle or leaves it — those are the
         # points where the plan can meaningfully change (lib/set.js:559-565)
         was_idle = {"v": False}
 
         def on_slot_state(new_state: str) -> None:
+            # Only the slot that is cs_fsm[key] does the bookkeeping
+            # below; a replacement in flight or a swapped-out
+            # predecessor is the age section's business.
+            if self.cs_age_slots is not None and \
+                    self._age_slot_state(key, fsm, new_state):
+                return
             if new_state == "idle":
                 self.emit("connectedToBackend", key, fsm)
                 if key in self.cs_dead:
@@ -517,6 +592,270 @@ class ConnectionSet(FSM):
 
         fsm.on("stateChanged", on_slot_state)
         fsm.start()
+
+    # -- connection age / recycle() ------------------------------------------
+    #
+    # Every connected socket may carry a deadline: its connect time plus
+    # a lifetime drawn once per socket (maxConnectionAge), or "now"
+    # (recycle()).  One call_at timer waits for the earliest deadline
+    # still ahead; everything else is driven by events the set sees
+    # anyway.  Unlike the pool, which closes an idle socket and lets the
+    # rebalance open another, a set replaces make-before-break: a second
+    # slot for the same backend is opened apart from cs_fsm (the
+    # rebalance planner never sees it), and only once its connection has
+    # been 'added' does it become cs_fsm[key] while the predecessor is
+    # drained and made unwanted.  One replacement at a time per set.
+
+    def _age_watch(self, fsm: ConnectionSlotFSM) -> None:
+        fsm.csf_smgr.on("stateChanged",
+                        functools.partial(self._age_smgr_changed, fsm))
+
+    def _age_draw(self, since: float) -> list:
+        life = self.cs_age_max * (1.0 - self.cs_age_spread * random.random())
+        return [since + life / 1000.0, "age"]
+
+    def _age_smgr_changed(self, fsm: ConnectionSlotFSM, st: str) -> None:
+        if st == "connected":
+            smgr = fsm.csf_smgr
+            if smgr.is_in_state("connected") and fsm.csf_wanted:
+                if self.cs_age_max is not None:
+                    self.cs_age_slots[fsm] = self._age_draw(
+                        smgr.sm_connected_at)
+                else:
+                    # a new socket: a recycle() mark was for the old one
+                    self.cs_age_slots.pop(fsm, None)
+            self._loop.call_soon(self._age_run)
+        elif st == "error" or st == "closed":
+            self.cs_age_slots.pop(fsm, None)
+            repl = self.cs_age_repl
+            if repl is not None and repl["old"] is fsm:
+                # the predecessor's socket died under its replacement
+                self._age_swap()
+
+    def _age_lconns(self,
+                    fsm: ConnectionSlotFSM) -> List["LogicalConnection"]:
+        """The live LogicalConnections that serve this very slot."""
+        out = []
+        for ck in self.cs_connection_keys.get(fsm.csf_backend["key"], ()):
+            lconn = self.cs_lconns.get(ck)
+            if lconn is not None and lconn.lc_fsm is fsm and \
+                    not lconn.is_in_state("stopped"):
+                out.append(lconn)
+        return out
+
+    def _age_advertised(self, fsm: ConnectionSlotFSM) -> Optional[str]:
+        """The ckey under which this slot's socket is advertised now:
+        'added' has been emitted, 'removed' has not, and the consumer
+        still holds the handle."""
+        for lconn in self._age_lconns(fsm):
+            if lconn.is_in_state("advertised") and \
+                    lconn.lc_hdl.is_in_state("claimed"):
+                return lconn.lc_ckey
+        return None
+
+    def _age_slot_state(self, key: str, fsm: ConnectionSlotFSM,
+                        st: str) -> bool:
+        """A slot changed state.  True if it is not the backend's slot
+        of record, so that the caller leaves cs_dead, cs_fsm and the
+        backend events alone."""
+        gone = st == "stopped" or st == "failed"
+        if gone:
+            self.cs_age_slots.pop(fsm, None)
+        repl = self.cs_age_repl
+        if gone and repl is not None and repl["old"] is fsm:
+            self._age_swap()
+            repl = None
+        if self.cs_fsm.get(key) is fsm:
+            return False
+        if repl is not None and repl["new"] is fsm:
+            if st == "failed":
+                self._age_failed()
+            return True
+        if gone:
+            self.cs_age_retired.pop(fsm, None)
+            self.rebalance()
+        return True
+
+    def _age_timer_fired(self) -> None:
+        at = self.cs_age_timer_at
+        self.cs_age_timer = None
+        self.cs_age_timer_at = None
+        # a loop may fire a timer a clock tick early
+        self._age_run(max(self._loop.time(), at))
+
+    def _age_run(self, now: Optional[float] = None) -> None:
+        """Start replacing what is due, oldest deadline first and one at
+        a time.  Then re-arm the timer."""
+        st = self._fsm_state
+        if st == "stopping" or st == "stopped":
+            return
+        if now is None:
+            now = self._loop.time()
+        slots = self.cs_age_slots
+        # only a running set starts a replacement; entering running
+        # brings us back here
+        if st == "running" and self.cs_age_repl is None:
+            due = [(ent[0], i, fsm) for i, (fsm, ent) in
+                   enumerate(slots.items()) if ent[0] <= now]
+            due.sort()
+            for _, _, fsm in due:
+                key = fsm.csf_backend["key"]
+                # due means advertised: anything else is on its way
+                # somewhere, and the event that ends it brings us back
+                if self.cs_fsm.get(key) is fsm and fsm.csf_wanted and \
+                        key in self.cs_backends and \
+                        self._age_advertised(fsm) is not None:
+                    self._age_replace(key, fsm)
+                    break
+        nxt: Optional[float] = None
+        for ent in slots.values():
+            if ent[0] > now and (nxt is None or ent[0] < nxt):
+                nxt = ent[0]
+        if nxt != self.cs_age_timer_at:
+            if self.cs_age_timer is not None:
+                self.cs_age_timer.cancel()
+                self.cs_age_timer = None
+            if nxt is not None:
+                self.cs_age_timer = self._loop.call_at(
+                    nxt, self._age_timer_fired)
+            self.cs_age_timer_at = nxt
+
+    def _age_replace(self, key: str, old: ConnectionSlotFSM) -> None:
+        """Open the replacement slot for `old`, apart from cs_fsm."""
+        reason = self.cs_age_slots.pop(old)[1]
+        new = self._make_slot(key, False)
+        self.cs_age_repl = {"key": key, "old": old, "new": new,
+                            "reason": reason}
+        self._start_slot(key, new)
+
+    def _age_swap(self) -> None:
+        """The replacement becomes the backend's slot and its
+        predecessor goes: either the successor has just been 'added',
+        or the predecessor went away by itself."""
+        repl = self.cs_age_repl
+        self.cs_age_repl = None
+        key, old, new, reason = (repl["key"], repl["old"], repl["new"],
+                                 repl["reason"])
+        self.cs_fsm[key] = new
+        if not (old.is_in_state("stopped") or old.is_in_state("failed")):
+            self.cs_age_retired[old] = key
+        self.emit("connectionRecycled", key, reason)
+        self._incr_counter("recycled-" + reason)
+        for lconn in self._age_lconns(old):
+            lconn.drain()
+        old.set_unwanted()
+        now = self._loop.time()
+        at = old.csf_smgr.sm_connected_at
+        old.csf_log.info(
+            'recycling connection to backend "%s" (%s) at age %d ms',
+            key, reason, round((now - at) * 1000.0) if at is not None else 0)
+        self.rebalance()
+        self._loop.call_soon(self._age_run)
+
+    def _age_failed(self) -> None:
+        """The replacement ran out of retries.  Its predecessor is alive
+        and advertised, so the backend is not dead: keep what we have."""
+        repl = self.cs_age_repl
+        self.cs_age_repl = None
+        key, old, reason = repl["key"], repl["old"], repl["reason"]
+        self._incr_counter("recycle-failed")
+        if reason == "age" and self.cs_age_max is not None and \
+                old.csf_smgr.is_in_state("connected"):
+            self.cs_age_slots[old] = self._age_draw(self._loop.time())
+        self.cs_log.warn('could not replace connection to backend "%s" '
+                         '(%s), keeping the old one' % (key, reason))
+        self.emit("connectionRecycleFailed", key, reason)
+        self._loop.call_soon(self._age_run)
+
+    def _age_cancel(self, key: Optional[str] = None) -> None:
+        """Give up the replacement in flight (for backend `key` only,
+        if given): its backend is leaving the set."""
+        repl = self.cs_age_repl
+        if repl is None or (key is not None and repl["key"] != key):
+            return
+        self.cs_age_repl = None
+        new = repl["new"]
+        if not (new.is_in_state("stopped") or new.is_in_state("failed")):
+            self.cs_age_retired[new] = repl["key"]
+        new.set_unwanted()
+        for lconn in self._age_lconns(new):
+            lconn.drain()
+        self._loop.call_soon(self._age_run)
+
+    def _age_stop(self) -> None:
+        self._age_cancel()
+        self.cs_age_slots.clear()
+        if self.cs_age_timer is not None:
+            self.cs_age_timer.cancel()
+            self.cs_age_timer = None
+            self.cs_age_timer_at = None
+
+    def recycle(self) -> int:
+        """Treat every socket that is connected and advertised right now
+        as expired: each is replaced make-before-break, one at a time.
+        Connections opened later are unaffected.  Returns the number of
+        connections marked (0 once the set is stopping, stopped or
+        failed)."""
+        if self._fsm_state not in ("starting", "running"):
+            return 0
+        if self.cs_age_slots is None:
+            self.cs_age_slots = {}
+            self.cs_age_retired = {}
+            for fsm in self.cs_fsm.values():
+                self._age_watch(fsm)
+        now = self._loop.time()
+        repl = self.cs_age_repl
+        marked = 0
+        for fsm in self.cs_fsm.values():
+            if (repl is not None and repl["old"] is fsm) or \
+                    not fsm.csf_wanted or \
+                    fsm.csf_smgr._fsm_state != "connected" or \
+                    self._age_advertised(fsm) is None:
+                continue
+            ent = self.cs_age_slots.get(fsm)
+            if ent is not None and ent[1] == "manual":
+                continue
+            at = now if ent is None or ent[0] > now else ent[0]
+            self.cs_age_slots[fsm] = [at, "manual"]
+            marked += 1
+        self._age_run(now)
+        return marked
+
+    def get_connection_ages(self) -> Dict[str, Any]:
+        """``{"maxAgeMs", "oldestMs", "connections": [{"backend",
+        "ckey", "state", "ageMs", "expiresInMs", "recycling"}, ...]}``;
+        ages and expiries are None for a slot without a connected
+        socket, ``expiresInMs`` also for a socket without a deadline,
+        ``ckey`` for a socket that is not advertised.  A replacement in
+        flight is listed after its predecessor, which is ``recycling``
+        from the moment the replacement is created until its socket is
+        closed."""
+        now = self._loop.time()
+        slots = self.cs_age_slots or {}
+        repl = self.cs_age_repl
+        listed = [(k, fsm, repl is not None and repl["old"] is fsm)
+                  for k, fsm in self.cs_fsm.items()]
+        if repl is not None:
+            listed.append((repl["key"], repl["new"], False))
+        for fsm, k in (self.cs_age_retired or {}).items():
+            listed.append((k, fsm, True))
+        out = []
+        oldest: Optional[float] = None
+        for k, fsm, recycling in listed:
+            smgr = fsm.csf_smgr
+            age = expires = None
+            if smgr._fsm_state == "connected":
+                age = (now - smgr.sm_connected_at) * 1000.0
+                if oldest is None or age > oldest:
+                    oldest = age
+                ent = slots.get(fsm)
+                if ent is not None:
+                    expires = max(0.0, (ent[0] - now) * 1000.0)
+            out.append({"backend": k, "ckey": self._age_advertised(fsm),
+                        "state": fsm.get_state(), "ageMs": age,
+                        "expiresInMs": expires, "recycling": recycling})
+        return {"maxAgeMs": self.cs_age_max, "oldestMs": oldest,
+                "connections": out}
 
     def _incr_counter(self, counter: str) -> None:
         mod_utils.update_error_metrics(self.cs_collector, self.cs_uuid,
