@@ -16,6 +16,9 @@ machinery (cueball_amd.http_client):
   through a retry driver (cueball_amd.retry): per-try and total
   timeouts, retries on another backend, a retry budget per host.
   ``add_request()`` with a caller-built request never retries.
+- the opt-in ``hedge`` option sends a slow ``request()`` a second time,
+  to another backend, and takes the first answer (cueball_amd.hedge);
+  with ``retry`` also on, every try of the retry driver is hedged.
 - ping checker: claims the exact idle socket and runs GET <ping>; a 5xx
   or error closes the connection, anything else releases it
   (lib/agent.js:398-455, PingAgent :530-569).
@@ -26,6 +29,7 @@ from __future__ import annotations
 import ssl as mod_ssl
 from typing import Any, Callable, Dict, Mapping, Optional
 
+from . import hedge as mod_hedge
 from . import retry as mod_retry
 from . import utils as mod_utils
 from .connection import TcpConnection
@@ -68,6 +72,14 @@ class Agent(EventEmitter):
     #: host -> retry.RetryHost: budget, counters, pending backoffs
     cba_retry_hosts: Optional[Dict[str, Any]] = None
     _retry_metrics: Optional[tuple] = None
+    # The hedge option's state, likewise.
+    #: the validated ``hedge`` option, defaults filled in
+    cba_hedge: Optional[Dict[str, Any]] = None
+    #: the same as the driver reads it (hedge.HedgePolicy)
+    cba_hedge_policy: Any = None
+    #: host -> hedge.HedgeHost: budget, latency window, counters
+    cba_hedge_hosts: Optional[Dict[str, Any]] = None
+    _hedge_metrics: Optional[tuple] = None
 
     def __init__(self, options: Dict[str, Any]) -> None:
         super().__init__()
@@ -136,6 +148,13 @@ class Agent(EventEmitter):
             self.cba_retry_policy = mod_retry.RetryPolicy(retry)
             self.cba_retry_hosts = {}
             self._register_retry_metrics()
+        # Request hedging (opt-in), likewise: see "hedging" below.
+        hedge = mod_utils.assert_hedge_policy(options)
+        if hedge is not None:
+            self.cba_hedge = hedge
+            self.cba_hedge_policy = mod_hedge.HedgePolicy(hedge)
+            self.cba_hedge_hosts = {}
+            self._register_hedge_metrics()
 
         for host in options.get("initialDomains") or ():
             self._add_pool(host, {})
@@ -324,6 +343,10 @@ class Agent(EventEmitter):
                                "new requests")
             for rhost in self.cba_retry_hosts.values():
                 rhost.stop(err)
+        if self.cba_hedge_hosts:
+            # no second attempt is started on a stopped agent
+            for hhost in self.cba_hedge_hosts.values():
+                hhost.stop()
         hosts = list(self.pools.keys())
         remaining = {"n": len(hosts)}
 
@@ -386,7 +409,8 @@ class Agent(EventEmitter):
         if host not in self.pools:
             self._add_pool(host, options)
         pool = self.pools[host]
-        if self.cba_retry is not None and isinstance(req, _TryRequest):
+        if (self.cba_retry is not None or self.cba_hedge is not None) \
+                and isinstance(req, _TryRequest):
             _TryTicket(self, pool, req)
         else:
             _RequestTicket(self, pool, req)
@@ -395,7 +419,7 @@ class Agent(EventEmitter):
                 path: str = "/", headers: Optional[Dict[str, str]] = None,
                 body: Optional[bytes] = None,
                 cb: Optional[Callable] = None,
-                retry: Any = None) -> Any:
+                retry: Any = None, hedge: Any = None) -> Any:
         """Convenience: run one request; cb(err, response) after the
         body has fully arrived.
 
@@ -403,17 +427,26 @@ class Agent(EventEmitter):
         the retry driver and a ``retry.RetriedRequest`` is returned;
         ``retry=False`` switches the driver off for this call, a
         mapping overrides keys of the agent's policy (all but
-        ``budget``) for this call."""
+        ``budget``) for this call.
+
+        On an agent with the ``hedge`` option the request, or each try
+        of the retry driver, is a ``hedge.HedgedTry``, which is what is
+        returned when only ``hedge`` is on; ``hedge=False`` switches
+        hedging off for this call, a mapping overrides keys of the
+        agent's policy (all but ``budget``, ``window`` and
+        ``minSamples``)."""
         if isinstance(options_or_host, str):
             host = options_or_host
         else:
             host = options_or_host.get("host")
-        if retry is not None or self.cba_retry is not None:
+        if retry is not None or self.cba_retry is not None or \
+                hedge is not None or self.cba_hedge is not None:
             policy = self._retry_policy_for(retry)
-            if policy is not None:
-                return self._request_retried(
-                    policy, options_or_host, host, method, path, headers,
-                    body, cb)
+            hpolicy = self._hedge_policy_for(hedge)
+            if policy is not None or hpolicy is not None:
+                return self._request_driven(
+                    policy, hpolicy, options_or_host, host, method, path,
+                    headers, body, cb)
         req = HttpRequest(method, path, headers=headers, body=body,
                           host=host)
 
@@ -433,7 +466,8 @@ class Agent(EventEmitter):
                             path: str = "/",
                             headers: Optional[Dict[str, str]] = None,
                             body: Optional[bytes] = None,
-                            retry: Any = None) -> HttpResponse:
+                            retry: Any = None,
+                            hedge: Any = None) -> HttpResponse:
         fut = self._loop.create_future()
 
         def cb(err: Optional[BaseException],
@@ -445,11 +479,11 @@ class Agent(EventEmitter):
             else:
                 fut.set_result(resp)
 
-        if retry is None:
+        if retry is None and hedge is None:
             self.request(options_or_host, method, path, headers, body, cb)
         else:
             self.request(options_or_host, method, path, headers, body, cb,
-                         retry=retry)
+                         retry=retry, hedge=hedge)
         return await fut
 
     # -- retries --------------------------------------------------------------
@@ -502,22 +536,22 @@ class Agent(EventEmitter):
         return mod_retry.RetryPolicy(
             mod_utils.override_retry_policy(self.cba_retry, retry))
 
-    def _request_retried(self, policy: Any, options_or_host: Any,
-                         host: Any, method: str, path: str,
-                         headers: Optional[Dict[str, str]],
-                         body: Optional[bytes],
-                         cb: Optional[Callable]) -> Any:
+    def _request_driven(self, policy: Any, hpolicy: Any,
+                        options_or_host: Any,
+                        host: Any, method: str, path: str,
+                        headers: Optional[Dict[str, str]],
+                        body: Optional[bytes],
+                        cb: Optional[Callable]) -> Any:
+        """One request under the retry driver (`policy`), the hedge
+        driver (`hpolicy`), or both: then every try of the retry driver
+        is a hedged one."""
         if not isinstance(host, str):
             if isinstance(options_or_host, Mapping):
                 host = options_or_host.get("hostname")
             if not isinstance(host, str):
                 raise TypeError("hostname is required")
-        rhost = self.cba_retry_hosts.get(host)
-        if rhost is None:
-            rhost = self.cba_retry_hosts[host] = mod_retry.RetryHost(
-                host, self.cba_retry["budget"], self._retry_counted)
 
-        def start_try(avoid: tuple) -> HttpRequest:
+        def start_real_try(avoid: tuple) -> HttpRequest:
             req = _TryRequest(method, path, headers=headers, body=body,
                               host=host)
             if avoid:
@@ -525,8 +559,37 @@ class Agent(EventEmitter):
             self.add_request(req, options_or_host)
             return req
 
-        rreq = mod_retry.RetriedRequest(self._loop, policy, rhost, method,
-                                        start_try, self.is_stopped)
+        if hpolicy is not None:
+            hhost = self.cba_hedge_hosts.get(host)
+            if hhost is None:
+                hhost = self.cba_hedge_hosts[host] = mod_hedge.HedgeHost(
+                    host, self.cba_hedge_policy, self._loop.time,
+                    self._hedge_counted, self._hedge_delay_changed)
+                if self.cba_hedge_policy.delay is not None:
+                    self._hedge_delay_changed(
+                        host, self.cba_hedge_policy.delay)
+
+            def has_idle(avoid: tuple) -> bool:
+                pool = self.pools.get(host)
+                return pool is not None and pool.has_idle_connection(avoid)
+
+            def hedged_try(avoid: tuple) -> Any:
+                return mod_hedge.HedgedTry(
+                    self._loop, hpolicy, hhost, method, start_real_try,
+                    avoid, has_idle, self.is_stopped)
+
+        if policy is None:
+            rreq = hedged_try(())
+        else:
+            rhost = self.cba_retry_hosts.get(host)
+            if rhost is None:
+                rhost = self.cba_retry_hosts[host] = mod_retry.RetryHost(
+                    host, self.cba_retry["budget"], self._retry_counted)
+            start_try = start_real_try if hpolicy is None else \
+                (lambda avoid: hedged_try(avoid).start())
+            rreq = mod_retry.RetriedRequest(self._loop, policy, rhost,
+                                            method, start_try,
+                                            self.is_stopped)
         if cb is not None:
             def on_resp(resp: HttpResponse) -> None:
                 if resp.complete:
@@ -544,6 +607,63 @@ class Agent(EventEmitter):
         budget.  Empty on an agent without ``retry``."""
         return {host: rhost.stats()
                 for host, rhost in (self.cba_retry_hosts or {}).items()}
+
+    # -- hedging ----------------------------------------------------------------
+    #
+    # With the ``hedge`` option, request() hands the request (or, under
+    # the retry driver, each of its tries) to a hedge.HedgedTry.  Its
+    # one or two attempts are _TryRequests like the tries of a retried
+    # request, so that the second one's claim can avoid the backend of
+    # the first.
+
+    def _register_hedge_metrics(self) -> None:
+        try:
+            self._hedge_metrics = (
+                self.collector.counter(
+                    name="cueball_agent_hedges_total",
+                    help="Hedged requests of the agent, by host and "
+                         "outcome"),
+                self.collector.gauge(
+                    name="cueball_agent_hedge_delay_seconds",
+                    help="The delay after which a request is hedged, "
+                         "by host"))
+        except (AttributeError, ValueError, TypeError):
+            self._hedge_metrics = None  # foreign collector
+
+    def _hedge_counted(self, host: str, counter: str) -> None:
+        metrics = self._hedge_metrics
+        if metrics is not None:
+            # "hedge-sent" -> outcome "sent"
+            metrics[0].increment({"host": host, "outcome": counter[6:]})
+
+    def _hedge_delay_changed(self, host: str, ms: float) -> None:
+        metrics = self._hedge_metrics
+        if metrics is not None:
+            metrics[1].set(ms / 1000.0, {"host": host})
+
+    def _hedge_policy_for(self, hedge: Any) -> Any:
+        """The hedge policy of one call, None for a call without
+        hedging."""
+        if hedge is None:
+            return self.cba_hedge_policy
+        if hedge is False:
+            return None
+        if self.cba_hedge is None:
+            if isinstance(hedge, Mapping):
+                raise ValueError("hedge= needs an agent that was created "
+                                 "with options.hedge")
+            raise TypeError("hedge= must be False or a mapping")
+        return mod_hedge.HedgePolicy(
+            mod_utils.override_hedge_policy(self.cba_hedge, hedge))
+
+    def get_hedge_stats(self) -> Dict[str, Any]:
+        """Per host that has seen a request under the driver: ``{"active",
+        "hedging", "limit", "delayMs", "samples", "latency",
+        "counters": {...}}``; ``delayMs`` is None while the adaptive
+        estimate has too few samples.  Empty on an agent without
+        ``hedge``."""
+        return {host: hhost.stats()
+                for host, hhost in (self.cba_hedge_hosts or {}).items()}
 
     # -- health checking -----------------------------------------------------
     def _check_socket(self, host: str, handle: Any, socket: Any) -> None:
@@ -656,7 +776,8 @@ class _RequestTicket:
 
 
 class _TryRequest(HttpRequest):
-    """One try of a retried request (see Agent._request_retried)."""
+    """One try of a retried request, or one attempt of a hedged try
+    (see Agent._request_driven)."""
 
     #: backend keys the try's claim is to avoid
     try_avoid: tuple = ()

@@ -1575,6 +1575,23 @@ class ConnectionPool(FSM):
             "waiterCount": len(self.p_waiters),
         }
 
+    def has_idle_connection(self, avoidBackends: Any = None) -> bool:
+        """Is a connection idle right now, on a backend that is not
+        among `avoidBackends` (an iterable of backend keys, as for
+        ``claim()``)?  A read-only walk of the idle queue: stale
+        entries are skipped, not unlinked.  Advisory: a claim's first
+        try runs on the next loop turn, and another claim may have
+        taken the slot by then."""
+        avoid = None
+        if avoidBackends is not None:
+            avoid = self._assert_avoid(avoidBackends)
+        for fsm in self.p_idleq:
+            if fsm.is_in_state("idle") and (
+                    avoid is None or
+                    fsm.csf_backend.get("key") not in avoid):
+                return True
+        return False
+
     def _idle_avoiding(self, avoid: frozenset) -> Optional[ConnectionSlotFSM]:
         """Unlink and return the first idle slot, in queue order, whose
         backend is not in `avoid`; the first idle slot of all when every

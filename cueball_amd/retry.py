@@ -25,7 +25,9 @@ backend keys to avoid and returns a *try*: an EventEmitter that emits
 ``error(err)``, and has ``abort()``.  Two attributes tell the driver
 where the try ran: ``try_backend``, the key of the backend it was
 claimed on (None for as long as it has no real socket), and
-``try_handle``, its claim handle (None likewise).
+``try_handle``, its claim handle (None likewise).  A try that ran on
+more than one backend (``hedge.HedgedTry``) also has ``try_backends``,
+a tuple of all of them; a failed try's backends are all avoided.
 """
 
 from __future__ import annotations
@@ -367,12 +369,17 @@ class RetriedRequest(EventEmitter):
         complete response whose status is selected (`resp`) or with
         `err`.  Retry, or end with that outcome."""
         t = self._try
-        key = getattr(t, "try_backend", None)
+        # a try that ran on more than one backend (hedge.HedgedTry)
+        # says so; a plain try ran on one, or on none
+        keys = getattr(t, "try_backends", None)
+        if keys is None:
+            key = getattr(t, "try_backend", None)
+            keys = () if key is None else (key,)
         self._drop_try(abort=abort)
         policy = self._policy
         host = self._host
         if self._wants_retry(reason):
-            if key is not None:
+            for key in keys:
                 if self._failed_on is None:
                     self._failed_on = [key]
                 elif key not in self._failed_on:

@@ -473,6 +473,132 @@ def override_retry_policy(policy: Optional[Mapping[str, Any]],
     return out
 
 
+_HEDGE_KEYS = ("delay", "percentile", "window", "minSamples", "minDelay",
+               "maxDelay", "methods", "budget")
+#: shared by every request to a host, so not for one call to change
+_HEDGE_SHARED_KEYS = ("budget", "window", "minSamples")
+
+
+def assert_hedge_policy(options: Mapping[str, Any]
+                        ) -> Optional[Dict[str, Any]]:
+    """Validate an agent's ``hedge`` option and return the policy with
+    every default filled in, or None when the option is off.  ``delay``
+    None means adaptive: a percentile of recent response times.
+    ``budget`` is a mapping ``{percent, minConcurrency}``; an explicit
+    None turns the budget off."""
+    hedge = options.get("hedge")
+    if hedge is None:
+        return None
+    name = "options.hedge"
+    if not isinstance(hedge, Mapping):
+        raise TypeError("%s must be a mapping" % name)
+    extra = set(hedge.keys()) - set(_HEDGE_KEYS)
+    if extra:
+        raise ValueError("%s has unknown keys: %r"
+                         % (name, sorted(extra, key=str)))
+
+    delay = _retry_ms(hedge.get("delay"), name + ".delay")
+
+    percentile = hedge.get("percentile")
+    if percentile is None:
+        percentile = 95
+    if not _num(percentile):
+        raise TypeError("%s.percentile must be a number" % name)
+    if not (0 < percentile < 100):
+        raise ValueError("%s.percentile must be in (0, 100)" % name)
+
+    window = _retry_ms(hedge.get("window"), name + ".window")
+    if window is None:
+        window = 10000
+
+    samples = hedge.get("minSamples")
+    if samples is None:
+        samples = 50
+    if not isinstance(samples, int) or isinstance(samples, bool):
+        raise TypeError("%s.minSamples must be an int" % name)
+    if samples < 1:
+        raise ValueError("%s.minSamples must be >= 1" % name)
+
+    min_delay = _retry_ms(hedge.get("minDelay"), name + ".minDelay")
+    if min_delay is None:
+        min_delay = 1
+    max_delay = hedge.get("maxDelay")
+    if max_delay is None:
+        max_delay = max(1000, min_delay)
+    if not _num(max_delay):
+        raise TypeError("%s.maxDelay must be a number" % name)
+    if not math.isfinite(max_delay) or max_delay < min_delay:
+        raise ValueError("%s.maxDelay must be finite and >= minDelay" % name)
+
+    methods = _retry_list(hedge.get("methods"), name + ".methods",
+                          ("GET", "HEAD", "OPTIONS"))
+    for method in methods:
+        if not isinstance(method, str):
+            raise TypeError("%s.methods must hold strings" % name)
+        if not method:
+            raise ValueError("%s.methods must not hold an empty string"
+                             % name)
+    methods = _retry_list([m.upper() for m in methods], "", ())
+
+    out: Dict[str, Any] = {
+        "delay": delay, "percentile": percentile, "window": window,
+        "minSamples": samples, "minDelay": min_delay, "maxDelay": max_delay,
+        "methods": methods}
+
+    if "budget" in hedge and hedge["budget"] is None:
+        out["budget"] = None
+        return out
+    budget = hedge.get("budget")
+    if budget is None:
+        budget = {}
+    bname = name + ".budget"
+    if not isinstance(budget, Mapping):
+        raise TypeError("%s must be a mapping or None" % bname)
+    extra = set(budget.keys()) - set(_RETRY_BUDGET_KEYS)
+    if extra:
+        raise ValueError("%s has unknown keys: %r"
+                         % (bname, sorted(extra, key=str)))
+    percent = budget.get("percent")
+    if percent is None:
+        percent = 10
+    if not _num(percent):
+        raise TypeError("%s.percent must be a number" % bname)
+    if not (0 <= percent <= 100):
+        raise ValueError("%s.percent must be in [0, 100]" % bname)
+    min_conc = budget.get("minConcurrency")
+    if min_conc is None:
+        min_conc = 1
+    if not isinstance(min_conc, int) or isinstance(min_conc, bool):
+        raise TypeError("%s.minConcurrency must be an int" % bname)
+    if min_conc < 0:
+        raise ValueError("%s.minConcurrency must be >= 0" % bname)
+    out["budget"] = {"percent": percent, "minConcurrency": min_conc}
+    return out
+
+
+def override_hedge_policy(policy: Optional[Mapping[str, Any]],
+                          override: Any) -> Dict[str, Any]:
+    """The policy of one call: `policy` (an agent's validated ``hedge``)
+    with the keys of `override` replaced and validated again.  Every
+    key may be overridden but ``budget``, ``window`` and ``minSamples``:
+    the budget and the latency window are shared by all requests to a
+    host."""
+    if policy is None:
+        raise ValueError("hedge= needs an agent that was created with "
+                         "options.hedge")
+    if not isinstance(override, Mapping):
+        raise TypeError("hedge= must be False or a mapping")
+    for k in _HEDGE_SHARED_KEYS:
+        if k in override:
+            raise ValueError("hedge= cannot override %s: it is shared by "
+                             "every request to the host" % k)
+    merged = dict(policy)
+    merged.update(override)
+    out = assert_hedge_policy({"hedge": merged})
+    assert out is not None
+    return out
+
+
 def plan_rebalance(connections: Mapping[str, Sequence[Any]],
                    dead: Mapping[str, bool],
                    target: int, maximum: int,
