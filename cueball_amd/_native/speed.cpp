@@ -22,6 +22,7 @@
 #include <Python.h>
 #include <structmember.h>
 #include <cmath>
+#include <cstring>
 #include <ctime>
 
 #include "lathist.h"
@@ -50,18 +51,86 @@ PyObject *g_flush_batches;     /* dict: loop -> _FlushBatch */
 PyObject *g_tracer;            /* optional fn(fsm, state) on transitions */
 PyObject *g_remove_desc;       /* EmitterType's remove_listener descriptor */
 
+/* get_loop(loop): a loop that is given is the answer; only None needs
+ * the python helper (running loop, else the policy's).  New reference. */
+static inline PyObject *
+resolve_loop(PyObject *loop)
+{
+    if (loop != NULL && loop != Py_None) {
+        Py_INCREF(loop);
+        return loop;
+    }
+    return PyObject_CallOneArg(g_get_loop, Py_None);
+}
+
 /* ------------------------------------------------------------------ */
 /* EventEmitter                                                        */
 /* ------------------------------------------------------------------ */
 
 typedef struct {
     PyObject_HEAD
-    PyObject *ev_events;   /* dict: str -> list of callables */
+    PyObject *ev_events;   /* dict: str -> list of callables; a list that
+                            * has been emptied stays (see
+                            * Emitter_remove_listener) */
     PyObject *ev_dict;     /* instance __dict__ (lazy) */
     PyObject *ev_weakrefs;
+    /* leak-detector cache (see emitter_leak_counts): ev_gen moves on
+     * every add/remove of a listener the detector could count */
+    unsigned long ev_gen;
+    unsigned long ev_lk_gen;    /* ev_gen the cache was filled at */
+    long ev_lk_cnt[4];          /* counted listeners per leak event */
+    Py_ssize_t ev_lk_len[4];    /* list lengths the counts belong to */
+    int ev_lk_ok;
 } Emitter;
 
 extern PyTypeObject EmitterType;
+extern PyTypeObject ConnErrCbType;
+extern PyTypeObject KitCbType;
+
+/* This module's own callback types answer _cueball_internal as true and
+ * are never counted by the leak detector, so (un)registering one leaves
+ * the cached counts valid. */
+static inline int
+listener_is_own_internal(PyObject *listener)
+{
+    PyTypeObject *tp = Py_TYPE(listener);
+    return tp == &ConnErrCbType || tp == &KitCbType;
+}
+
+/* Listener lists on the claim cycle go 0 -> 1 -> 0 entries every cycle.
+ * list.append / slice deletion give the item array back to the
+ * allocator at 0 and fetch it again at 1; these two keep a small array
+ * in place. */
+#define SMALL_LIST_KEEP 8
+
+static inline int
+list_append_keep(PyObject *ls, PyObject *item)
+{
+    PyListObject *l = (PyListObject *)ls;
+    Py_ssize_t n = Py_SIZE(l);
+    if (n < l->allocated) {
+        Py_INCREF(item);
+        l->ob_item[n] = item;
+        Py_SET_SIZE(l, n + 1);
+        return 0;
+    }
+    return PyList_Append(ls, item);
+}
+
+static inline int
+list_remove_at_keep(PyObject *ls, Py_ssize_t i)
+{
+    PyListObject *l = (PyListObject *)ls;
+    Py_ssize_t n = Py_SIZE(l);
+    if (l->allocated > SMALL_LIST_KEEP)
+        return PyList_SetSlice(ls, i, i + 1, NULL);
+    PyObject *item = l->ob_item[i];
+    for (Py_ssize_t j = i; j + 1 < n; j++)
+        l->ob_item[j] = l->ob_item[j + 1];
+    Py_SET_SIZE(l, n - 1);
+    Py_DECREF(item);
+    return 0;
+}
 
 int
 Emitter_init(PyObject *self_, PyObject *args, PyObject *kwds)
@@ -128,8 +197,10 @@ emitter_add(Emitter *self, PyObject *event, PyObject *listener)
         }
         Py_DECREF(ls);  /* dict holds it */
     }
-    if (PyList_Append(ls, listener) < 0)
+    if (list_append_keep(ls, listener) < 0)
         return NULL;
+    if (!listener_is_own_internal(listener))
+        self->ev_gen++;
     Py_INCREF(listener);
     return listener;
 }
@@ -312,12 +383,14 @@ Emitter_remove_listener(PyObject *self_, PyObject *const *args,
         }
     }
     if (found >= 0) {
-        if (PyList_SetSlice(ls, found, found + 1, NULL) < 0)
+        if (!listener_is_own_internal(PyList_GET_ITEM(ls, found)))
+            self->ev_gen++;
+        /* an emptied list stays in ev_events: the scoped registrations
+         * of the claim cycle would otherwise delete and re-create it
+         * (and its key) every cycle.  Everything that reports events
+         * treats an empty list as absent. */
+        if (list_remove_at_keep(ls, found) < 0)
             return NULL;
-        if (PyList_GET_SIZE(ls) == 0) {
-            if (PyDict_DelItem(self->ev_events, args[0]) < 0)
-                PyErr_Clear();
-        }
     }
     Py_RETURN_NONE;
 }
@@ -329,6 +402,7 @@ Emitter_remove_all_listeners(PyObject *self_, PyObject *const *args,
     Emitter *self = (Emitter *)self_;
     if (self->ev_events == NULL)
         Py_RETURN_NONE;
+    self->ev_gen++;
     if (nargs == 0 || args[0] == Py_None) {
         PyDict_Clear(self->ev_events);
     } else {
@@ -372,9 +446,21 @@ Emitter_event_names(PyObject *self_, PyObject *noargs)
 {
     Emitter *self = (Emitter *)self_;
     (void)noargs;
-    if (self->ev_events == NULL)
-        return PyList_New(0);
-    return PyDict_Keys(self->ev_events);
+    PyObject *names = PyList_New(0);
+    if (names == NULL || self->ev_events == NULL)
+        return names;
+    PyObject *key, *ls;
+    Py_ssize_t pos = 0;
+    while (PyDict_Next(self->ev_events, &pos, &key, &ls)) {
+        /* emptied lists are kept (Emitter_remove_listener) */
+        if (PyList_Check(ls) && PyList_GET_SIZE(ls) == 0)
+            continue;
+        if (PyList_Append(names, key) < 0) {
+            Py_DECREF(names);
+            return NULL;
+        }
+    }
+    return names;
 }
 
 /* emit with node snapshot semantics */
@@ -495,12 +581,47 @@ int fsm_goto_state(FSMOb *fsm, PyObject *state);
 typedef struct {
     PyObject_HEAD
     PyObject *sc_fsm;       /* FSMOb*, strong */
-    PyObject *sc_listeners; /* flat list [em, evt, cb, ...] or NULL */
+    PyObject *sc_listeners; /* flat list [em, evt, cb, ...] of the
+                             * registrations beyond sc_reg, or NULL */
     PyObject *sc_timers;    /* list of cancellables or NULL */
     int sc_active;
+    int sc_nreg;            /* registrations held in sc_reg */
+    PyObject *sc_reg[3 * 4];/* the first four (em, evt, cb), owned: the
+                             * states of the claim cycle register at
+                             * most two, so they allocate nothing */
 } Scope;
 
+#define SCOPE_INLINE_REGS 4
+
 extern PyTypeObject ScopeType;
+
+/* Freed scopes are kept for the next transition (one is made per
+ * transition, six per claim cycle). */
+#define SCOPE_FREELIST_MAX 32
+Scope *scope_freelist[SCOPE_FREELIST_MAX];
+int scope_freelist_n = 0;
+
+Scope *
+scope_new(PyObject *fsm)
+{
+    Scope *scope;
+    if (scope_freelist_n > 0) {
+        scope = scope_freelist[--scope_freelist_n];
+        _Py_NewReference((PyObject *)scope);
+    } else {
+        scope = PyObject_GC_New(Scope, &ScopeType);
+        if (scope == NULL)
+            return NULL;
+    }
+    Py_INCREF(fsm);
+    scope->sc_fsm = fsm;
+    scope->sc_listeners = NULL;
+    scope->sc_timers = NULL;
+    scope->sc_active = 1;
+    scope->sc_nreg = 0;
+    PyObject_GC_Track((PyObject *)scope);
+    return scope;
+}
 
 /* guarded zero/N-arg callback: no-op once scope inactive */
 typedef struct {
@@ -599,6 +720,17 @@ scope_on_c(Scope *self, PyObject *emitter, PyObject *event, PyObject *cb)
     if (r == NULL)
         return -1;
     Py_DECREF(r);
+    if (self->sc_nreg < SCOPE_INLINE_REGS) {
+        PyObject **slot = self->sc_reg + 3 * self->sc_nreg;
+        Py_INCREF(emitter);
+        slot[0] = emitter;
+        Py_INCREF(event);
+        slot[1] = event;
+        Py_INCREF(cb);
+        slot[2] = cb;
+        self->sc_nreg++;
+        return 0;
+    }
     if (self->sc_listeners == NULL) {
         self->sc_listeners = PyList_New(0);
         if (self->sc_listeners == NULL)
@@ -722,41 +854,69 @@ Scope_goto_state(PyObject *self_, PyObject *state)
     Py_RETURN_NONE;
 }
 
+/* undo one S.on() registration */
+int
+scope_unregister(PyObject *em, PyObject *evt, PyObject *cb)
+{
+    PyObject *r;
+    /* fast path only when the type's MRO resolves remove_listener to
+     * our own C method (no override) */
+    int fast = 0;
+    if (PyType_IsSubtype(Py_TYPE(em), &EmitterType)) {
+        PyObject *desc = _PyType_Lookup(Py_TYPE(em), s_remove_listener);
+        fast = (desc == g_remove_desc);
+    }
+    if (fast) {
+        PyObject *cargs[2] = {evt, cb};
+        r = Emitter_remove_listener(em, cargs, 2);
+    } else {
+        r = PyObject_CallMethodObjArgs(em, s_remove_listener, evt, cb,
+                                       NULL);
+    }
+    if (r == NULL)
+        return -1;
+    Py_DECREF(r);
+    return 0;
+}
+
 PyObject *
 Scope_dispose(PyObject *self_, PyObject *noargs)
 {
     Scope *self = (Scope *)self_;
     (void)noargs;
     self->sc_active = 0;
+    /* take the registrations out first: removing a listener can run
+     * arbitrary code, which may come back here */
+    PyObject *regs[3 * SCOPE_INLINE_REGS];
+    int nreg = self->sc_nreg;
+    self->sc_nreg = 0;
+    for (int i = 0; i < 3 * nreg; i++)
+        regs[i] = self->sc_reg[i];
     PyObject *ls = self->sc_listeners;
     self->sc_listeners = NULL;
+    int failed = 0;
+    for (int i = 0; i < nreg; i++) {
+        if (!failed &&
+            scope_unregister(regs[3 * i], regs[3 * i + 1],
+                             regs[3 * i + 2]) < 0)
+            failed = 1;
+        Py_DECREF(regs[3 * i]);
+        Py_DECREF(regs[3 * i + 1]);
+        Py_DECREF(regs[3 * i + 2]);
+    }
+    if (failed) {
+        Py_XDECREF(ls);
+        return NULL;
+    }
     if (ls != NULL) {
         Py_ssize_t n = PyList_GET_SIZE(ls);
         for (Py_ssize_t i = 0; i + 2 < n; i += 3) {
-            PyObject *em = PyList_GET_ITEM(ls, i);
-            PyObject *evt = PyList_GET_ITEM(ls, i + 1);
-            PyObject *cb = PyList_GET_ITEM(ls, i + 2);
-            PyObject *r;
-            /* fast path only when the type's MRO resolves
-             * remove_listener to our own C method (no override) */
-            int fast = 0;
-            if (PyType_IsSubtype(Py_TYPE(em), &EmitterType)) {
-                PyObject *desc = _PyType_Lookup(Py_TYPE(em),
-                                                s_remove_listener);
-                fast = (desc == g_remove_desc);
-            }
-            if (fast) {
-                PyObject *cargs[2] = {evt, cb};
-                r = Emitter_remove_listener(em, cargs, 2);
-            } else {
-                r = PyObject_CallMethodObjArgs(em, s_remove_listener, evt,
-                                               cb, NULL);
-            }
-            if (r == NULL) {
+            if (scope_unregister(PyList_GET_ITEM(ls, i),
+                                 PyList_GET_ITEM(ls, i + 1),
+                                 PyList_GET_ITEM(ls, i + 2)) < 0) {
                 Py_DECREF(ls);
                 return NULL;
             }
-            Py_DECREF(r);
         }
         Py_DECREF(ls);
     }
@@ -792,6 +952,8 @@ Scope_traverse(PyObject *self_, visitproc visit, void *arg)
     Py_VISIT(self->sc_fsm);
     Py_VISIT(self->sc_listeners);
     Py_VISIT(self->sc_timers);
+    for (int i = 0; i < 3 * self->sc_nreg; i++)
+        Py_VISIT(self->sc_reg[i]);
     return 0;
 }
 
@@ -802,6 +964,10 @@ Scope_clear_(PyObject *self_)
     Py_CLEAR(self->sc_fsm);
     Py_CLEAR(self->sc_listeners);
     Py_CLEAR(self->sc_timers);
+    int nreg = self->sc_nreg;
+    self->sc_nreg = 0;
+    for (int i = 0; i < 3 * nreg; i++)
+        Py_CLEAR(self->sc_reg[i]);
     return 0;
 }
 
@@ -810,7 +976,10 @@ Scope_dealloc(PyObject *self_)
 {
     PyObject_GC_UnTrack(self_);
     Scope_clear_(self_);
-    PyObject_GC_Del(self_);
+    if (scope_freelist_n < SCOPE_FREELIST_MAX)
+        scope_freelist[scope_freelist_n++] = (Scope *)self_;
+    else
+        PyObject_GC_Del(self_);
 }
 
 PyMethodDef Scope_methods[] = {
@@ -860,8 +1029,17 @@ struct FSMOb {
     PyObject *f_scope;          /* Scope* or NULL */
     PyObject *f_valid;          /* sequence or NULL */
     PyObject *f_pending;        /* str or NULL */
-    PyObject *f_emit_queue;     /* list */
-    PyObject *f_history;        /* list */
+    /* queued stateChanged emissions, oldest at f_eq_head.  They live in
+     * f_eq_inl until more than FSM_EQ_INLINE are pending at once, then
+     * in a malloc'ed array; popping moves the head, and the array is
+     * compacted once per flush */
+    PyObject **f_eq;            /* f_eq_inl or heap */
+    Py_ssize_t f_eq_head, f_eq_len, f_eq_cap;
+    PyObject *f_eq_inl[4];
+    /* the last FSM_HISTORY states as a ring; f_hist_n counts every
+     * transition, the newest is at (f_hist_n - 1) % FSM_HISTORY */
+    PyObject *f_hist[8];
+    unsigned long f_hist_n;
     PyObject *f_flush_bound;    /* cached bound _flush_state_changed */
     PyObject *f_fastkit;        /* SlotKit* or NULL: native entries for
                                  * the busy/idle hot cycle */
@@ -881,12 +1059,82 @@ extern PyTypeObject CHType;
 extern PyTypeObject CTType;
 void ch_terminal_cleanup(FSMOb *self);
 
+/* the claim handle's C state entry for `target`, if the type of `self`
+ * still resolves that entry to it (no Python override); else NULL */
+typedef PyObject *(*ch_entry_fn)(PyObject *, PyObject *);
+ch_entry_fn ch_direct_entry(FSMOb *self, PyObject *target);
+
 extern PyTypeObject FSMType;
 
 PyObject *
 fsm_get_loop_of(FSMOb *fsm)
 {
     return fsm->f_loop;
+}
+
+#define FSM_EQ_INLINE 4
+#define FSM_HISTORY 8
+
+static void
+fsm_eq_compact(FSMOb *f)
+{
+    if (f->f_eq_head == 0)
+        return;
+    Py_ssize_t n = f->f_eq_len - f->f_eq_head;
+    memmove(f->f_eq, f->f_eq + f->f_eq_head, n * sizeof(PyObject *));
+    f->f_eq_head = 0;
+    f->f_eq_len = n;
+}
+
+static int
+fsm_eq_push(FSMOb *f, PyObject *st)
+{
+    if (f->f_eq == NULL) {
+        f->f_eq = f->f_eq_inl;
+        f->f_eq_cap = FSM_EQ_INLINE;
+        f->f_eq_head = f->f_eq_len = 0;
+    }
+    if (f->f_eq_len == f->f_eq_cap) {
+        if (f->f_eq_head > 0) {
+            fsm_eq_compact(f);
+        } else {
+            Py_ssize_t ncap = f->f_eq_cap * 2;
+            PyObject **items;
+            if (f->f_eq == f->f_eq_inl) {
+                items = (PyObject **)PyMem_Malloc(
+                    ncap * sizeof(PyObject *));
+                if (items != NULL)
+                    memcpy(items, f->f_eq_inl, sizeof(f->f_eq_inl));
+            } else {
+                items = (PyObject **)PyMem_Realloc(
+                    f->f_eq, ncap * sizeof(PyObject *));
+            }
+            if (items == NULL) {
+                PyErr_NoMemory();
+                return -1;
+            }
+            f->f_eq = items;
+            f->f_eq_cap = ncap;
+        }
+    }
+    Py_INCREF(st);
+    f->f_eq[f->f_eq_len++] = st;
+    return 0;
+}
+
+static void
+fsm_eq_clear(FSMOb *f)
+{
+    PyObject **items = f->f_eq;
+    Py_ssize_t head = f->f_eq_head, len = f->f_eq_len;
+    f->f_eq = NULL;
+    f->f_eq_head = f->f_eq_len = f->f_eq_cap = 0;
+    if (items == NULL)
+        return;
+    for (Py_ssize_t i = head; i < len; i++)
+        Py_DECREF(items[i]);
+    if (items != f->f_eq_inl)
+        PyMem_Free(items);
 }
 
 int fsm_schedule_flush(FSMOb *self);
@@ -902,22 +1150,22 @@ fsm_flush_core(FSMOb *self)
 {
     self->f_emit_scheduled = 0;
     int n = 0;
-    while (PyList_GET_SIZE(self->f_emit_queue) > 0 &&
-           n++ < FSM_FLUSH_CAP) {
-        PyObject *st = PyList_GET_ITEM(self->f_emit_queue, 0);
-        Py_INCREF(st);
-        if (PyList_SetSlice(self->f_emit_queue, 0, 1, NULL) < 0) {
-            Py_DECREF(st);
-            return -1;
-        }
+    while (self->f_eq_head < self->f_eq_len && n++ < FSM_FLUSH_CAP) {
+        /* pop by index; listeners may queue more (or flush again)
+         * while they run, so the queue is read afresh every turn */
+        PyObject *st = self->f_eq[self->f_eq_head++];
+        if (self->f_eq_head == self->f_eq_len)
+            self->f_eq_head = self->f_eq_len = 0;
         PyObject *eargs[2] = {s_stateChanged, st};
         int r = emitter_emit_core(&self->base, eargs[0], eargs + 1, 1);
         Py_DECREF(st);
-        if (r < 0)
+        if (r < 0) {
+            fsm_eq_compact(self);
             return -1;
+        }
     }
-    if (PyList_GET_SIZE(self->f_emit_queue) > 0 &&
-        !self->f_emit_scheduled)
+    fsm_eq_compact(self);
+    if (self->f_eq_len > 0 && !self->f_emit_scheduled)
         return fsm_schedule_flush(self);
     return 0;
 }
@@ -1055,7 +1303,7 @@ PyTypeObject FlushBatchType = {
 int
 fsm_queue_state_changed(FSMOb *self, PyObject *state)
 {
-    if (PyList_Append(self->f_emit_queue, state) < 0)
+    if (fsm_eq_push(self, state) < 0)
         return -1;
     return fsm_schedule_flush(self);
 }
@@ -1170,27 +1418,14 @@ fsm_enter_loop(FSMOb *self, PyObject *state)
         Py_CLEAR(self->f_valid);
         Py_INCREF(target);
         Py_XSETREF(self->f_state, target);
-        if (PyList_Append(self->f_history, target) < 0) {
-            Py_DECREF(target);
-            return -1;
-        }
-        if (PyList_GET_SIZE(self->f_history) > 8) {
-            if (PyList_SetSlice(self->f_history, 0, 1, NULL) < 0) {
-                Py_DECREF(target);
-                return -1;
-            }
-        }
-        Scope *scope = PyObject_GC_New(Scope, &ScopeType);
+        Py_INCREF(target);
+        Py_XSETREF(self->f_hist[self->f_hist_n % FSM_HISTORY], target);
+        self->f_hist_n++;
+        Scope *scope = scope_new((PyObject *)self);
         if (scope == NULL) {
             Py_DECREF(target);
             return -1;
         }
-        Py_INCREF((PyObject *)self);
-        scope->sc_fsm = (PyObject *)self;
-        scope->sc_listeners = NULL;
-        scope->sc_timers = NULL;
-        scope->sc_active = 1;
-        PyObject_GC_Track((PyObject *)scope);
         Py_INCREF((PyObject *)scope);
         Py_XSETREF(self->f_scope, (PyObject *)scope);
 
@@ -1218,10 +1453,18 @@ fsm_enter_loop(FSMOb *self, PyObject *state)
             }
         }
         PyObject *r;
+        ch_entry_fn direct = handled ? NULL : ch_direct_entry(self, target);
         if (handled) {
             Py_DECREF(scope);
             r = Py_None;
             Py_INCREF(r);
+        } else if (direct != NULL) {
+            /* the type's entry for this state is this module's own C
+             * function: call it without building a bound method */
+            self->f_entering = 1;
+            r = direct((PyObject *)self, (PyObject *)scope);
+            Py_DECREF(scope);
+            self->f_entering = 0;
         } else {
             PyObject *attr = entry_attr_name(target);
             if (attr == NULL) {
@@ -1321,20 +1564,10 @@ FSM_init(PyObject *self_, PyObject *args, PyObject *kwds)
         return -1;
     if (Emitter_init(self_, NULL, NULL) < 0)
         return -1;
-    PyObject *resolved = PyObject_CallOneArg(g_get_loop, loop);
+    PyObject *resolved = resolve_loop(loop);
     if (resolved == NULL)
         return -1;
     Py_XSETREF(self->f_loop, resolved);
-    if (self->f_emit_queue == NULL) {
-        self->f_emit_queue = PyList_New(0);
-        if (self->f_emit_queue == NULL)
-            return -1;
-    }
-    if (self->f_history == NULL) {
-        self->f_history = PyList_New(0);
-        if (self->f_history == NULL)
-            return -1;
-    }
     Py_CLEAR(self->f_state);
     Py_CLEAR(self->f_valid);
     Py_CLEAR(self->f_pending);
@@ -1384,8 +1617,19 @@ FSM_get_state_history(PyObject *self_, PyObject *noargs)
 {
     FSMOb *self = (FSMOb *)self_;
     (void)noargs;
-    return PyList_GetSlice(self->f_history, 0,
-                           PyList_GET_SIZE(self->f_history));
+    Py_ssize_t count = self->f_hist_n < FSM_HISTORY
+        ? (Py_ssize_t)self->f_hist_n : FSM_HISTORY;
+    PyObject *out = PyList_New(count);
+    if (out == NULL)
+        return NULL;
+    unsigned long first = self->f_hist_n - (unsigned long)count;
+    for (Py_ssize_t i = 0; i < count; i++) {
+        PyObject *st = self->f_hist[(first + (unsigned long)i) %
+                                    FSM_HISTORY];
+        Py_INCREF(st);
+        PyList_SET_ITEM(out, i, st);
+    }
+    return out;
 }
 
 PyObject *
@@ -1600,8 +1844,10 @@ FSM_traverse(PyObject *self_, visitproc visit, void *arg)
     Py_VISIT(self->f_scope);
     Py_VISIT(self->f_valid);
     Py_VISIT(self->f_pending);
-    Py_VISIT(self->f_emit_queue);
-    Py_VISIT(self->f_history);
+    for (Py_ssize_t i = self->f_eq_head; i < self->f_eq_len; i++)
+        Py_VISIT(self->f_eq[i]);
+    for (int i = 0; i < FSM_HISTORY; i++)
+        Py_VISIT(self->f_hist[i]);
     Py_VISIT(self->f_flush_bound);
     Py_VISIT(self->f_fastkit);
     return Emitter_traverse(self_, visit, arg);
@@ -1616,8 +1862,10 @@ FSM_clear_(PyObject *self_)
     Py_CLEAR(self->f_scope);
     Py_CLEAR(self->f_valid);
     Py_CLEAR(self->f_pending);
-    Py_CLEAR(self->f_emit_queue);
-    Py_CLEAR(self->f_history);
+    fsm_eq_clear(self);
+    for (int i = 0; i < FSM_HISTORY; i++)
+        Py_CLEAR(self->f_hist[i]);
+    self->f_hist_n = 0;
     Py_CLEAR(self->f_flush_bound);
     Py_CLEAR(self->f_fastkit);
     return Emitter_clear_(self_);
@@ -1689,6 +1937,127 @@ PyTypeObject FSMType = {
     0, 0, 0,
     0,                                    /* tp_dictoffset (inherited) */
     FSM_init,
+    0,
+    PyType_GenericNew,
+};
+
+/* ------------------------------------------------------------------ */
+/* SlotBase: native base of ConnectionSlotFSM.  It only holds the      */
+/* fields that the claim cycle reads and writes from C several times   */
+/* per claim, as struct members under their Python names, so neither   */
+/* side goes through the instance dict for them.  An unset field reads */
+/* as None.  The flags are objects: any truthy value works.            */
+
+typedef struct {
+    FSMOb base;
+    PyObject *sl_handle;        /* csf_handle */
+    PyObject *sl_prev_handle;   /* csf_prev_handle */
+    PyObject *sl_wanted;        /* csf_wanted */
+    PyObject *sl_monitor;       /* csf_monitor */
+    PyObject *sl_idleq_node;    /* p_idleq_node */
+    PyObject *sl_initq_node;    /* p_initq_node */
+} SlotOb;
+
+extern PyTypeObject SlotBaseType;
+
+static inline int
+slot_field_set(PyObject **field)
+{
+    return *field != NULL && *field != Py_None;
+}
+
+static inline int
+slot_field_true(PyObject **field)
+{
+    PyObject *v = *field;
+    if (v == Py_True)
+        return 1;
+    if (v == NULL || v == Py_False || v == Py_None)
+        return 0;
+    Py_INCREF(v);
+    int t = PyObject_IsTrue(v);
+    Py_DECREF(v);
+    return t;
+}
+
+static inline void
+slot_field_store(PyObject **field, PyObject *value)
+{
+    Py_XINCREF(value);
+    Py_XSETREF(*field, value);
+}
+
+int
+Slot_traverse(PyObject *self_, visitproc visit, void *arg)
+{
+    SlotOb *self = (SlotOb *)self_;
+    Py_VISIT(self->sl_handle);
+    Py_VISIT(self->sl_prev_handle);
+    Py_VISIT(self->sl_wanted);
+    Py_VISIT(self->sl_monitor);
+    Py_VISIT(self->sl_idleq_node);
+    Py_VISIT(self->sl_initq_node);
+    return FSM_traverse(self_, visit, arg);
+}
+
+int
+Slot_clear_(PyObject *self_)
+{
+    SlotOb *self = (SlotOb *)self_;
+    Py_CLEAR(self->sl_handle);
+    Py_CLEAR(self->sl_prev_handle);
+    Py_CLEAR(self->sl_wanted);
+    Py_CLEAR(self->sl_monitor);
+    Py_CLEAR(self->sl_idleq_node);
+    Py_CLEAR(self->sl_initq_node);
+    return FSM_clear_(self_);
+}
+
+void
+Slot_dealloc(PyObject *self_)
+{
+    SlotOb *self = (SlotOb *)self_;
+    PyTypeObject *tp = Py_TYPE(self_);
+    PyObject_GC_UnTrack(self_);
+    if (self->base.base.ev_weakrefs != NULL)
+        PyObject_ClearWeakRefs(self_);
+    Slot_clear_(self_);
+    tp->tp_free(self_);
+}
+
+PyMemberDef Slot_members[] = {
+    {(char *)"csf_handle", T_OBJECT, offsetof(SlotOb, sl_handle), 0, NULL},
+    {(char *)"csf_prev_handle", T_OBJECT, offsetof(SlotOb, sl_prev_handle),
+     0, NULL},
+    {(char *)"csf_wanted", T_OBJECT, offsetof(SlotOb, sl_wanted), 0, NULL},
+    {(char *)"csf_monitor", T_OBJECT, offsetof(SlotOb, sl_monitor), 0,
+     NULL},
+    {(char *)"p_idleq_node", T_OBJECT, offsetof(SlotOb, sl_idleq_node), 0,
+     NULL},
+    {(char *)"p_initq_node", T_OBJECT, offsetof(SlotOb, sl_initq_node), 0,
+     NULL},
+    {NULL, 0, 0, 0, NULL},
+};
+
+PyTypeObject SlotBaseType = {
+    PyVarObject_HEAD_INIT(NULL, 0)
+    "cueball_amd._speed.SlotBase",
+    sizeof(SlotOb),
+    0,
+    Slot_dealloc,
+    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+    Py_TPFLAGS_DEFAULT | Py_TPFLAGS_BASETYPE | Py_TPFLAGS_HAVE_GC,
+    "connection slot FSM (native fields)",
+    Slot_traverse,
+    Slot_clear_,
+    0, 0, 0, 0,
+    0,
+    Slot_members,
+    0,
+    &FSMType,
+    0, 0, 0,
+    0,
+    0,                                    /* tp_init (inherited) */
     0,
     PyType_GenericNew,
 };
@@ -2086,9 +2455,27 @@ PyObject *t_claimed_valid;       /* ("released","closed") */
 PyObject *t_empty;               /* () */
 PyObject *s_leak_events[4];      /* close, error, readable, data */
 
+/* mirror of utils.enable/disable_stack_traces(): while capture is off
+ * (the default) the shared placeholder list is used without a call */
+int g_stack_on = 1;              /* until python tells us otherwise */
+PyObject *g_stack_placeholder;   /* utils._DISABLED_STACK */
+PyObject *g_inf;                 /* float('inf'): the no-timeout claim */
+
+static inline PyObject *
+capture_stack(void)
+{
+    if (!g_stack_on && g_stack_placeholder != NULL) {
+        Py_INCREF(g_stack_placeholder);
+        return g_stack_placeholder;
+    }
+    return PyObject_CallNoArgs(g_capture_stack);
+}
+
 /* defined in the SlotKit section below */
 extern PyObject *s_busy_st;
-extern PyObject *s_csf_handle;
+/* the slot kit's preallocated conn-error callback for `handle` claimed
+ * on `slot` (borrowed), or NULL if the slot has no kit */
+PyObject *slotkit_conn_err_cb(PyObject *slot, PyObject *handle);
 
 typedef struct {
     FSMOb base;
@@ -2100,6 +2487,8 @@ typedef struct {
     PyObject *chb_release_stack;
     PyObject *chb_connection;
     PyObject *chb_last_error;
+    PyObject *chb_waiter_node; /* ch_waiter_node: NULL or None unless
+                                * the handle sits in the waiter queue */
     PoolLatOb *chb_lat;     /* the pool's latency recorder, or NULL */
     double chb_claim_timeout;
     double chb_started;
@@ -2176,6 +2565,56 @@ c_count_listeners(PyObject *emitter, PyObject *event)
     return count;
 }
 
+/* The leak detector's four counts (s_leak_events order) of user
+ * listeners on a connection.  Returns 0, -1 on error, or -2 when the
+ * connection is not a native emitter (not ours: nothing is counted).
+ * In steady state the listeners of a pooled connection are the same
+ * from one claim to the next, so the counts are cached on the emitter,
+ * tagged with its generation and the four list lengths (the lengths
+ * catch a list changed behind the emitter's back, through _events);
+ * with the tag intact this costs four dict lookups instead of a walk
+ * over every listener with two attribute lookups each. */
+int
+emitter_leak_counts(PyObject *conn, long out[4])
+{
+    if (!PyObject_TypeCheck(conn, &EmitterType))
+        return -2;
+    Emitter *em = (Emitter *)conn;
+    Py_ssize_t lens[4];
+    for (int i = 0; i < 4; i++) {
+        PyObject *ls = NULL;
+        if (em->ev_events != NULL) {
+            ls = PyDict_GetItemWithError(em->ev_events, s_leak_events[i]);
+            if (ls == NULL && PyErr_Occurred())
+                return -1;
+        }
+        lens[i] = (ls != NULL && PyList_Check(ls)) ? PyList_GET_SIZE(ls)
+                                                   : -1;
+    }
+    if (em->ev_lk_ok && em->ev_lk_gen == em->ev_gen &&
+        memcmp(lens, em->ev_lk_len, sizeof(lens)) == 0) {
+        memcpy(out, em->ev_lk_cnt, sizeof(em->ev_lk_cnt));
+        return 0;
+    }
+    unsigned long gen = em->ev_gen;
+    for (int i = 0; i < 4; i++) {
+        long c = c_count_listeners(conn, s_leak_events[i]);
+        if (c < 0)
+            return -1;
+        out[i] = c;
+    }
+    /* counting reads attributes of the listeners, which may run code:
+     * keep the result only if no listener came or went meanwhile */
+    em->ev_lk_ok = 0;
+    if (gen == em->ev_gen) {
+        memcpy(em->ev_lk_cnt, out, sizeof(em->ev_lk_cnt));
+        memcpy(em->ev_lk_len, lens, sizeof(lens));
+        em->ev_lk_gen = gen;
+        em->ev_lk_ok = 1;
+    }
+    return 0;
+}
+
 /* claimed-state conn-error listener: raise if the user has no error
  * listener (and throw_error), else warn + count */
 typedef struct {
@@ -2185,6 +2624,8 @@ typedef struct {
 
 extern PyTypeObject ConnErrCbType;
 
+PyObject *conn_err_fire(CHOb *h, PyObject *err);
+
 PyObject *
 ConnErrCb_call(PyObject *self_, PyObject *args, PyObject *kwds)
 {
@@ -2192,6 +2633,13 @@ ConnErrCb_call(PyObject *self_, PyObject *args, PyObject *kwds)
     (void)kwds;
     PyObject *err = (PyTuple_GET_SIZE(args) > 0)
         ? PyTuple_GET_ITEM(args, 0) : Py_None;
+    return conn_err_fire(h, err);
+}
+
+/* shared by _ConnErrCb and the slot kit's preallocated twin */
+PyObject *
+conn_err_fire(CHOb *h, PyObject *err)
+{
     long cnt = c_count_listeners(h->chb_connection, s_error_evt);
     if (cnt == -1)
         return NULL;
@@ -2500,7 +2948,7 @@ ch_relinquish(CHOb *self, PyObject *target_state)
         Py_DECREF(msg);
         return -1;
     }
-    PyObject *stack = PyObject_CallNoArgs(g_capture_stack);
+    PyObject *stack = capture_stack();
     if (stack == NULL)
         return -1;
     Py_XSETREF(self->chb_release_stack, stack);
@@ -2572,7 +3020,7 @@ CH_state_claiming(PyObject *self_, PyObject *scope)
     PyObject *slot = self->chb_slot;
     /* inline of ConnectionSlotFSM.claim() when the slot runs the
      * native busy/idle cycle (same checks, same transition) */
-    if (slot != NULL && PyObject_TypeCheck(slot, &FSMType) &&
+    if (slot != NULL && PyObject_TypeCheck(slot, &SlotBaseType) &&
         ((FSMOb *)slot)->f_fastkit != NULL) {
         FSMOb *sf = (FSMOb *)slot;
         PyObject *fs = sf->f_state;
@@ -2581,17 +3029,11 @@ CH_state_claiming(PyObject *self_, PyObject *scope)
             PyErr_SetString(g_fsm_error, "claim only in idle");
             return NULL;
         }
-        PyObject *cur = PyObject_GetAttr(slot, s_csf_handle);
-        if (cur == NULL)
-            return NULL;
-        int has = (cur != Py_None);
-        Py_DECREF(cur);
-        if (has) {
+        if (slot_field_set(&((SlotOb *)slot)->sl_handle)) {
             PyErr_SetString(g_fsm_error, "slot already has a handle");
             return NULL;
         }
-        if (PyObject_SetAttr(slot, s_csf_handle, self_) < 0)
-            return NULL;
+        slot_field_store(&((SlotOb *)slot)->sl_handle, self_);
         if (fsm_goto_state(sf, s_busy_st) < 0)
             return NULL;
         Py_RETURN_NONE;
@@ -2618,21 +3060,29 @@ CH_state_claimed(PyObject *self_, PyObject *scope)
     }
 
     PyObject *conn = self->chb_connection;
-    for (int i = 0; i < 4; i++) {
-        long c = c_count_listeners(conn, s_leak_events[i]);
-        if (c == -1)
-            return NULL;
-        self->chb_pre[i] = (c == -2) ? 0 : c;
-    }
+    int lk = emitter_leak_counts(conn, self->chb_pre);
+    if (lk == -1)
+        return NULL;
+    if (lk == -2)
+        self->chb_pre[0] = self->chb_pre[1] = self->chb_pre[2] =
+            self->chb_pre[3] = 0;
     self->chb_have_pre = 1;
 
-    ConnErrCb *ec = PyObject_GC_New(ConnErrCb, &ConnErrCbType);
-    if (ec == NULL)
-        return NULL;
-    Py_INCREF(self_);
-    ec->ce_handle = self_;
-    PyObject_GC_Track((PyObject *)ec);
-    PyObject *args[3] = {conn, s_error_evt, (PyObject *)ec};
+    /* the slot's kit keeps one error callback for all its claims; a
+     * handle claimed any other way gets one of its own */
+    PyObject *ec = slotkit_conn_err_cb(self->chb_slot, self_);
+    if (ec != NULL) {
+        Py_INCREF(ec);
+    } else {
+        ConnErrCb *nec = PyObject_GC_New(ConnErrCb, &ConnErrCbType);
+        if (nec == NULL)
+            return NULL;
+        Py_INCREF(self_);
+        nec->ce_handle = self_;
+        PyObject_GC_Track((PyObject *)nec);
+        ec = (PyObject *)nec;
+    }
+    PyObject *args[3] = {conn, s_error_evt, ec};
     PyObject *r = Scope_on(scope, args, 3);
     Py_DECREF(ec);
     if (r == NULL)
@@ -2687,11 +3137,17 @@ CH_state_released(PyObject *self_, PyObject *scope)
     if (!self->chb_leak_check || !self->chb_have_pre)
         Py_RETURN_NONE;
     PyObject *conn = self->chb_connection;
+    /* with no listener added or removed since the "before" reading
+     * this answers from the emitter's cache without a walk */
+    long after[4];
+    int lk = emitter_leak_counts(conn, after);
+    if (lk == -1)
+        return NULL;
+    if (lk == -2)
+        Py_RETURN_NONE;
     for (int i = 0; i < 4; i++) {
-        long c = c_count_listeners(conn, s_leak_events[i]);
-        if (c == -1)
-            return NULL;
-        if (c != -2 && c > self->chb_pre[i]) {
+        long c = after[i];
+        if (c > self->chb_pre[i]) {
             PyObject *msg = PyUnicode_FromFormat(
                 "connection claimer looks like it leaked event handlers "
                 "(event=%S before=%ld after=%ld)",
@@ -2819,6 +3275,7 @@ CH_traverse(PyObject *self_, visitproc visit, void *arg)
     Py_VISIT(self->chb_release_stack);
     Py_VISIT(self->chb_connection);
     Py_VISIT(self->chb_last_error);
+    Py_VISIT(self->chb_waiter_node);
     Py_VISIT((PyObject *)self->chb_lat);
     return FSM_traverse(self_, visit, arg);
 }
@@ -2835,6 +3292,7 @@ CH_clear_(PyObject *self_)
     Py_CLEAR(self->chb_release_stack);
     Py_CLEAR(self->chb_connection);
     Py_CLEAR(self->chb_last_error);
+    Py_CLEAR(self->chb_waiter_node);
     Py_CLEAR(self->chb_lat);
     return FSM_clear_(self_);
 }
@@ -2887,22 +3345,12 @@ CH__setup(PyObject *self_, PyObject *const *args, Py_ssize_t nargs)
     Py_XSETREF(self->chb_lat, (PoolLatOb *)lat);
 
     /* FSM init (resolves loop, enters "waiting") */
-    PyObject *resolved = PyObject_CallOneArg(g_get_loop, args[6]);
+    PyObject *resolved = resolve_loop(args[6]);
     if (resolved == NULL)
         return NULL;
     Py_XSETREF(self->base.f_loop, resolved);
     if (Emitter_init(self_, NULL, NULL) < 0)
         return NULL;
-    if (self->base.f_emit_queue == NULL) {
-        self->base.f_emit_queue = PyList_New(0);
-        if (self->base.f_emit_queue == NULL)
-            return NULL;
-    }
-    if (self->base.f_history == NULL) {
-        self->base.f_history = PyList_New(0);
-        if (self->base.f_history == NULL)
-            return NULL;
-    }
     if (fsm_goto_state(&self->base, s_waiting) < 0)
         return NULL;
     if (self->chb_lat != NULL && self->chb_lat->pl_direct &&
@@ -2965,6 +3413,8 @@ PyMemberDef CH_members[] = {
      0, NULL},
     {(char *)"ch_last_error", T_OBJECT, offsetof(CHOb, chb_last_error),
      0, NULL},
+    {(char *)"ch_waiter_node", T_OBJECT, offsetof(CHOb, chb_waiter_node),
+     0, NULL},
     {(char *)"ch_claim_timeout", T_DOUBLE,
      offsetof(CHOb, chb_claim_timeout), 0, NULL},
     {(char *)"ch_started", T_DOUBLE, offsetof(CHOb, chb_started), 0, NULL},
@@ -3006,6 +3456,87 @@ PyTypeObject CHType = {
     0,
     PyType_GenericNew,
 };
+
+/* direct dispatch of the handle's state entries (fsm_enter_loop) */
+struct ChEntry {
+    PyObject **ce_state;     /* interned state name */
+    const char *ce_method;
+    ch_entry_fn ce_fn;
+    PyObject *ce_attr;       /* interned method name */
+    PyObject *ce_desc;       /* CHType's own descriptor for it */
+};
+
+ChEntry ch_entries[] = {
+    {&s_waiting, "state_waiting", CH_state_waiting, NULL, NULL},
+    {&s_claiming, "state_claiming", CH_state_claiming, NULL, NULL},
+    {&s_claimed, "state_claimed", CH_state_claimed, NULL, NULL},
+    {&s_released, "state_released", CH_state_released, NULL, NULL},
+    {&s_closed, "state_closed", CH_state_closed, NULL, NULL},
+    {&s_cancelled, "state_cancelled", CH_state_cancelled, NULL, NULL},
+    {&s_failed, "state_failed", CH_state_failed, NULL, NULL},
+};
+const int ch_n_entries = (int)(sizeof(ch_entries) / sizeof(ch_entries[0]));
+
+int
+ch_entries_init(void)
+{
+    for (int i = 0; i < ch_n_entries; i++) {
+        ChEntry *e = &ch_entries[i];
+        e->ce_attr = PyUnicode_InternFromString(e->ce_method);
+        if (e->ce_attr == NULL)
+            return -1;
+        e->ce_desc = PyDict_GetItemWithError(CHType.tp_dict, e->ce_attr);
+        if (e->ce_desc == NULL)
+            return -1;
+        Py_INCREF(e->ce_desc);
+    }
+    return 0;
+}
+
+ch_entry_fn
+ch_direct_entry(FSMOb *self, PyObject *target)
+{
+    PyTypeObject *tp = Py_TYPE(self);
+    if (!PyType_IsSubtype(tp, &CHType))
+        return NULL;
+    for (int i = 0; i < ch_n_entries; i++) {
+        ChEntry *e = &ch_entries[i];
+        if (*e->ce_state != target)
+            continue;
+        /* same test Scope_dispose applies to remove_listener: the MRO
+         * still resolves the name to our own method, and (a method is
+         * a non-data descriptor) the instance does not shadow it */
+        if (_PyType_Lookup(tp, e->ce_attr) != e->ce_desc)
+            return NULL;
+        PyObject *d = self->base.ev_dict;
+        if (d != NULL && PyDict_GET_SIZE(d) > 0 &&
+            PyDict_GetItemWithError(d, e->ce_attr) != NULL)
+            return NULL;
+        if (PyErr_Occurred())
+            PyErr_Clear();
+        return e->ce_fn;
+    }
+    return NULL;
+}
+
+PyObject *
+speed_set_stack_traces(PyObject *mod, PyObject *const *args,
+                       Py_ssize_t nargs)
+{
+    (void)mod;
+    if (nargs != 2) {
+        PyErr_SetString(PyExc_TypeError,
+                        "_set_stack_traces(enabled, placeholder)");
+        return NULL;
+    }
+    int on = PyObject_IsTrue(args[0]);
+    if (on < 0)
+        return NULL;
+    g_stack_on = on;
+    Py_INCREF(args[1]);
+    Py_XSETREF(g_stack_placeholder, args[1]);
+    Py_RETURN_NONE;
+}
 
 PyObject *
 speed_set_claim_helpers(PyObject *mod, PyObject *const *args,
@@ -3481,6 +4012,9 @@ PyObject *s_p_total_conns;   /* "p_total_conns" */
 PyObject *s_p_busy_hwm;      /* "p_busy_hwm" */
 PyObject *s_p_demand_hwm;    /* "p_demand_hwm" */
 PyObject *s_ticket_slow;     /* "_ticket_slow" */
+PyObject *s_p_idleq;         /* "p_idleq" */
+PyObject *s_p_waiters;       /* "p_waiters" */
+PyObject *s_p_initq;         /* "p_initq" */
 
 typedef struct {
     PyObject_HEAD
@@ -3500,9 +4034,9 @@ extern PyTypeObject CTType;
 static void
 ct_bind_queues(CTOb *t, PyObject *pool)
 {
-    PyObject *iq = PyObject_GetAttrString(pool, "p_idleq");
-    PyObject *wq = iq ? PyObject_GetAttrString(pool, "p_waiters") : NULL;
-    PyObject *nq = wq ? PyObject_GetAttrString(pool, "p_initq") : NULL;
+    PyObject *iq = PyObject_GetAttr(pool, s_p_idleq);
+    PyObject *wq = iq ? PyObject_GetAttr(pool, s_p_waiters) : NULL;
+    PyObject *nq = wq ? PyObject_GetAttr(pool, s_p_initq) : NULL;
     if (nq == NULL) {
         PyErr_Clear();
         Py_XDECREF(iq);
@@ -3581,7 +4115,6 @@ ct_note_demand(CTOb *t)
 }
 
 PyObject *s_p_counters;          /* "p_counters" */
-PyObject *s_ch_waiter_node;      /* "ch_waiter_node" */
 PyObject *s_p_rebal_scheduled;   /* "p_rebal_scheduled" */
 PyObject *s_max_claim_queue;     /* "max-claim-queue" */
 PyObject *s_queued_claim;        /* "queued-claim" */
@@ -3599,11 +4132,7 @@ ct_enqueue_waiter(CTOb *t)
     /* the handle keeps its node so leaving 'waiting' (timeout/
      * cancel) unlinks it immediately — overload cannot accumulate
      * dead queue entries between feeds (see pool._ticket_slow) */
-    int rc = PyObject_SetAttr(t->ct_handle, s_ch_waiter_node,
-                              (PyObject *)n);
-    Py_DECREF((PyObject *)n);
-    if (rc < 0)
-        return -1;
+    Py_XSETREF(((CHOb *)t->ct_handle)->chb_waiter_node, (PyObject *)n);
     if (ct_note_demand(t) < 0)
         return -1;
 
@@ -3717,7 +4246,9 @@ ct_try_next(CTOb *t)
         Py_DECREF((PyObject *)n);
         if (fsm == NULL)
             continue;
-        if (PyObject_SetAttr(fsm, s_p_idleq_node, Py_None) < 0) {
+        if (PyObject_TypeCheck(fsm, &SlotBaseType)) {
+            slot_field_store(&((SlotOb *)fsm)->sl_idleq_node, Py_None);
+        } else if (PyObject_SetAttr(fsm, s_p_idleq_node, Py_None) < 0) {
             Py_DECREF(fsm);
             return -1;
         }
@@ -3910,19 +4441,13 @@ speed_pool_claim(PyObject *mod, PyObject *const *args, Py_ssize_t nargs)
     if (bad)
         Py_RETURN_TRUE;
 
-    PyObject *stack = PyObject_CallNoArgs(g_capture_stack);
+    PyObject *stack = capture_stack();
     if (stack == NULL)
         return NULL;
-    PyObject *inf = PyFloat_FromDouble(HUGE_VAL);
-    if (inf == NULL) {
-        Py_DECREF(stack);
-        return NULL;
-    }
     PyObject *cfargs[8] = {args[0], pool, stack, args[2], args[3],
-                           inf, args[4], Py_False};
+                           g_inf, args[4], Py_False};
     PyObject *h = speed_claim_fast(NULL, cfargs, 8);
     Py_DECREF(stack);
-    Py_DECREF(inf);
     return h;
 }
 
@@ -4020,17 +4545,13 @@ ch_terminal_cleanup(FSMOb *self)
 {
     /* unlink from the waiter queue if still queued (timeout/cancel
      * while waiting): keeps the queue free of dead entries */
-    PyObject *wn = PyObject_GetAttr((PyObject *)self, s_ch_waiter_node);
-    if (wn == NULL) {
-        PyErr_Clear();
-    } else {
+    PyObject *wn = ((CHOb *)self)->chb_waiter_node;
+    if (wn != NULL) {
+        ((CHOb *)self)->chb_waiter_node = NULL;
         if (PyObject_TypeCheck(wn, &QNodeType) &&
             ((QNode *)wn)->q_queue != NULL)
             nqueue_unlink(((QNode *)wn)->q_queue, (QNode *)wn);
         Py_DECREF(wn);
-        if (PyObject_SetAttr((PyObject *)self, s_ch_waiter_node,
-                             Py_None) < 0)
-            PyErr_Clear();
     }
     if (self->f_scope != NULL) {
         PyObject *old = self->f_scope;
@@ -4066,8 +4587,15 @@ ch_terminal_cleanup(FSMOb *self)
 /* SlotKit: native entries for ConnectionSlotFSM's busy/idle hot       */
 /* cycle (connection_fsm.py state_busy/state_idle).  One claim/release */
 /* runs idle -> busy -> idle; with the kit installed both entries and  */
-/* their event callbacks execute in C, with zero per-cycle Python      */
-/* allocation.  Installed only for slots without a health checker;     */
+/* their event callbacks execute in C.  The kit's callbacks (the four  */
+/* listeners of the two states and the claimed handle's conn-error     */
+/* listener) are allocated once per slot, the four registrations of a  */
+/* cycle sit in their scopes' inline arrays, and the listener lists    */
+/* they go into keep their storage; what the slot's side of a cycle    */
+/* still allocates is its two scopes, taken from a freelist.  (The     */
+/* claim itself allocates a handle, a ticket and the handle's event    */
+/* dict and listener list.)  Installed only for slots without a health */
+/* checker;                                                            */
 /* monitor/unwanted idle entries fall back to the Python entry, and    */
 /* all exit transitions out of the cycle enter Python states.          */
 
@@ -4079,10 +4607,6 @@ PyObject *s_retrying_st;     /* "retrying" */
 PyObject *s_connecting_st;   /* "connecting" */
 PyObject *s_killing_st;      /* "killing" */
 PyObject *s_unwanted_evt;    /* "unwanted" */
-PyObject *s_csf_handle;      /* "csf_handle" */
-PyObject *s_csf_prev_handle; /* "csf_prev_handle" */
-PyObject *s_csf_wanted;      /* "csf_wanted" */
-PyObject *s_csf_monitor;     /* "csf_monitor" */
 PyObject *s_sm_socket;       /* "sm_socket" */
 PyObject *t_busy_valid;      /* like _BUSY_VALID */
 PyObject *t_idle_valid;      /* like _IDLE_VALID */
@@ -4090,7 +4614,8 @@ PyObject *t_idle_valid;      /* like _IDLE_VALID */
 typedef struct SlotKit SlotKit;
 
 /* preallocated listener callables; `which` selects the behavior */
-enum { KCB_BUSY_SMGR = 0, KCB_BUSY_HDL, KCB_IDLE_SMGR, KCB_IDLE_UNWANTED };
+enum { KCB_BUSY_SMGR = 0, KCB_BUSY_HDL, KCB_IDLE_SMGR, KCB_IDLE_UNWANTED,
+       KCB_CONN_ERR, KCB_N };
 
 typedef struct {
     PyObject_HEAD
@@ -4105,21 +4630,23 @@ struct SlotKit {
     PyObject *k_observed;       /* event-observed smgr state, owned */
     Scope *k_busy_scope;        /* owned; scope of the last busy entry */
     Scope *k_idle_scope;        /* owned; scope of the last idle entry */
-    PyObject *k_cbs[4];         /* owned KitCb instances */
+    PyObject *k_cbs[KCB_N];        /* owned KitCb instances */
 };
 
 extern PyTypeObject SlotKitType;
 extern PyTypeObject KitCbType;
 
-static int
-kit_truthy_attr(PyObject *obj, PyObject *name)
+PyObject *
+slotkit_conn_err_cb(PyObject *slot, PyObject *handle)
 {
-    PyObject *v = PyObject_GetAttr(obj, name);
-    if (v == NULL)
-        return -1;
-    int t = PyObject_IsTrue(v);
-    Py_DECREF(v);
-    return t;
+    if (slot == NULL || !PyObject_TypeCheck(slot, &SlotBaseType))
+        return NULL;
+    PyObject *kit = ((FSMOb *)slot)->f_fastkit;
+    if (kit == NULL || Py_TYPE(kit) != &SlotKitType ||
+        ((SlotKit *)kit)->k_slot != (FSMOb *)slot ||
+        ((SlotOb *)slot)->sl_handle != handle)
+        return NULL;
+    return ((SlotKit *)kit)->k_cbs[KCB_CONN_ERR];
 }
 
 static int
@@ -4135,7 +4662,7 @@ kit_busy_on_release(SlotKit *k)
 {
     Scope *S = k->k_busy_scope;
     PyObject *st = k->k_observed;
-    int wanted = kit_truthy_attr((PyObject *)k->k_slot, s_csf_wanted);
+    int wanted = slot_field_true(&((SlotOb *)k->k_slot)->sl_wanted);
     if (wanted < 0)
         return -1;
     if (st == s_connected_st ||
@@ -4166,7 +4693,7 @@ static int
 kit_idle_smgr_changed(SlotKit *k, PyObject *st)
 {
     Scope *S = k->k_idle_scope;
-    int wanted = kit_truthy_attr((PyObject *)k->k_slot, s_csf_wanted);
+    int wanted = slot_field_true(&((SlotOb *)k->k_slot)->sl_wanted);
     if (wanted < 0)
         return -1;
     if (st == s_error_evt || PyUnicode_Compare(st, s_error_evt) == 0)
@@ -4227,6 +4754,19 @@ KitCb_call(PyObject *self_, PyObject *args, PyObject *kwds)
     case KCB_IDLE_UNWANTED:
         r = kit_idle_unwanted(k);
         break;
+    case KCB_CONN_ERR: {
+        /* registered by the claimed state of the slot's current handle
+         * and removed when that state is left, so the handle is the
+         * slot's */
+        PyObject *hdl = ((SlotOb *)k->k_slot)->sl_handle;
+        if (hdl == NULL || !PyObject_TypeCheck(hdl, &CHType))
+            break;
+        Py_INCREF(hdl);
+        PyObject *res = conn_err_fire((CHOb *)hdl,
+                                      st != NULL ? st : Py_None);
+        Py_DECREF(hdl);
+        return res;
+    }
     }
     if (r < 0)
         return NULL;
@@ -4270,9 +4810,10 @@ kit_state_busy(SlotKit *k, Scope *scope)
     Py_INCREF(t_busy_valid);
     Py_XSETREF(slot->f_valid, t_busy_valid);
 
-    PyObject *hdl = PyObject_GetAttr((PyObject *)slot, s_csf_handle);
+    PyObject *hdl = ((SlotOb *)slot)->sl_handle;
     if (hdl == NULL)
-        return -1;
+        hdl = Py_None;
+    Py_INCREF(hdl);
     Py_INCREF(s_connected_st);
     Py_XSETREF(k->k_observed, s_connected_st);
     Py_INCREF((PyObject *)scope);
@@ -4311,9 +4852,7 @@ kit_state_busy(SlotKit *k, Scope *scope)
         if (r == NULL)
             return -1;
         Py_DECREF(r);
-        if (PyObject_SetAttr((PyObject *)slot, s_csf_handle,
-                             Py_None) < 0)
-            return -1;
+        slot_field_store(&((SlotOb *)slot)->sl_handle, Py_None);
         if (kit_busy_on_release(k) < 0)
             return -1;
     }
@@ -4326,12 +4865,12 @@ kit_state_idle(SlotKit *k, Scope *scope)
     FSMOb *slot = k->k_slot;
     /* the monitor-conversion and unwanted cases keep the full Python
      * entry (cold paths with documented divergences) */
-    int monitor = kit_truthy_attr((PyObject *)slot, s_csf_monitor);
+    int monitor = slot_field_true(&((SlotOb *)slot)->sl_monitor);
     if (monitor < 0)
         return -1;
     if (monitor)
         return 0;
-    int wanted = kit_truthy_attr((PyObject *)slot, s_csf_wanted);
+    int wanted = slot_field_true(&((SlotOb *)slot)->sl_wanted);
     if (wanted < 0)
         return -1;
     if (!wanted)
@@ -4342,22 +4881,16 @@ kit_state_idle(SlotKit *k, Scope *scope)
     Py_INCREF((PyObject *)scope);
     Py_XSETREF(k->k_idle_scope, scope);
 
-    PyObject *hdl = PyObject_GetAttr((PyObject *)slot, s_csf_handle);
-    if (hdl == NULL)
-        return -1;
-    if (hdl != Py_None) {
-        if (PyObject_SetAttr((PyObject *)slot, s_csf_prev_handle,
-                             hdl) < 0) {
-            Py_DECREF(hdl);
-            return -1;
-        }
-        if (PyObject_SetAttr((PyObject *)slot, s_csf_handle,
-                             Py_None) < 0) {
-            Py_DECREF(hdl);
-            return -1;
-        }
+    SlotOb *so = (SlotOb *)slot;
+    if (slot_field_set(&so->sl_handle)) {
+        /* csf_prev_handle = csf_handle; csf_handle = None.  The old
+         * previous handle is let go last: freeing it can run code */
+        PyObject *old_prev = so->sl_prev_handle;
+        so->sl_prev_handle = so->sl_handle;
+        Py_INCREF(Py_None);
+        so->sl_handle = Py_None;
+        Py_XDECREF(old_prev);
     }
-    Py_DECREF(hdl);
 
     if (scope_on_c(scope, k->k_smgr, s_stateChanged,
                    k->k_cbs[KCB_IDLE_SMGR]) < 0)
@@ -4685,7 +5218,6 @@ codel_type_init(void)
 
 PyObject *s_p_backends;          /* "p_backends" */
 PyObject *s_p_dead;              /* "p_dead" */
-PyObject *s_p_initq_node;        /* "p_initq_node" */
 PyObject *s_connected_to_backend;/* "connectedToBackend" */
 PyObject *s_slot_state_changed;  /* "_slot_state_changed" */
 PyObject *s_remove_node;         /* "remove" */
@@ -4731,11 +5263,8 @@ SlotDispatch_call(PyObject *self_, PyObject *args, PyObject *kwds)
     FSMOb *fsm = (FSMOb *)d->sd_fsm;
 
     /* common preconditions for both fast paths */
-    PyObject *initq_node = PyObject_GetAttr(d->sd_fsm, s_p_initq_node);
-    if (initq_node == NULL)
-        return NULL;
-    int in_initq = (initq_node != Py_None);
-    Py_DECREF(initq_node);
+    SlotOb *so = (SlotOb *)d->sd_fsm;
+    int in_initq = slot_field_set(&so->sl_initq_node);
 
     if (!in_initq &&
         (st == s_busy_st ||
@@ -4743,20 +5272,12 @@ SlotDispatch_call(PyObject *self_, PyObject *args, PyObject *kwds)
           PyUnicode_Compare(st, s_busy_st) == 0))) {
         /* busy: with no pinger handle and no stale idleq node this
          * dispatch is a no-op */
-        PyObject *idleq_node = PyObject_GetAttr(d->sd_fsm,
-                                                s_p_idleq_node);
-        if (idleq_node == NULL)
-            return NULL;
-        int linked = (idleq_node != Py_None);
-        Py_DECREF(idleq_node);
-        if (!linked) {
-            PyObject *hdl = PyObject_GetAttr(d->sd_fsm, s_csf_handle);
-            if (hdl == NULL)
-                return NULL;
+        if (!slot_field_set(&so->sl_idleq_node)) {
+            PyObject *hdl = so->sl_handle;
             int pinger = 0;
-            if (hdl != Py_None && PyObject_TypeCheck(hdl, &CHType))
+            if (hdl != NULL && hdl != Py_None &&
+                PyObject_TypeCheck(hdl, &CHType))
                 pinger = ((CHOb *)hdl)->chb_pinger;
-            Py_DECREF(hdl);
             if (!pinger)
                 Py_RETURN_NONE;
         }
@@ -4795,29 +5316,21 @@ SlotDispatch_call(PyObject *self_, PyObject *args, PyObject *kwds)
               (fs != NULL && PyUnicode_Compare(fs, s_idle) == 0))) {
             /* the event already emitted above; only the trailing
              * was-idle-now-isn't unlink branch can still apply */
-            PyObject *idn = PyObject_GetAttr(d->sd_fsm,
-                                             s_p_idleq_node);
-            if (idn == NULL)
-                return NULL;
-            if (idn != Py_None) {
+            if (slot_field_set(&so->sl_idleq_node)) {
+                PyObject *idn = so->sl_idleq_node;
+                Py_INCREF(idn);
                 PyObject *rr = PyObject_CallMethodObjArgs(
                     idn, s_remove_node, NULL);
-                if (rr == NULL) {
-                    Py_DECREF(idn);
-                    return NULL;
-                }
-                Py_DECREF(rr);
                 Py_DECREF(idn);
-                if (PyObject_SetAttr(d->sd_fsm, s_p_idleq_node,
-                                     Py_None) < 0)
+                if (rr == NULL)
                     return NULL;
+                Py_DECREF(rr);
+                slot_field_store(&so->sl_idleq_node, Py_None);
                 PyObject *rb = PyObject_CallMethodObjArgs(
                     d->sd_pool, s_rebalance, NULL);
                 if (rb == NULL)
                     return NULL;
                 Py_DECREF(rb);
-            } else {
-                Py_DECREF(idn);
             }
             Py_RETURN_NONE;
         }
@@ -4889,11 +5402,7 @@ SlotDispatch_call(PyObject *self_, PyObject *args, PyObject *kwds)
         QNode *n = nqueue_push(d->sd_idleq, d->sd_fsm);
         if (n == NULL)
             return NULL;
-        int rc = PyObject_SetAttr(d->sd_fsm, s_p_idleq_node,
-                                  (PyObject *)n);
-        Py_DECREF((PyObject *)n);
-        if (rc < 0)
-            return NULL;
+        Py_XSETREF(so->sl_idleq_node, (PyObject *)n);
         Py_RETURN_NONE;
     }
 
@@ -4944,7 +5453,7 @@ SlotDispatch_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
     if (!PyArg_ParseTuple(args, "OOOO", &pool, &fsm, &key, &has_codel))
         return NULL;
     if (!PyObject_TypeCheck(pool, &EmitterType) ||
-        !PyObject_TypeCheck(fsm, &FSMType)) {
+        !PyObject_TypeCheck(fsm, &SlotBaseType)) {
         PyErr_SetString(PyExc_TypeError,
                         "SlotDispatch(pool, slot, key, has_codel)");
         return NULL;
@@ -5007,7 +5516,7 @@ SlotKit_traverse(PyObject *self_, visitproc visit, void *arg)
     Py_VISIT(k->k_observed);
     Py_VISIT((PyObject *)k->k_busy_scope);
     Py_VISIT((PyObject *)k->k_idle_scope);
-    for (int i = 0; i < 4; i++)
+    for (int i = 0; i < KCB_N; i++)
         Py_VISIT(k->k_cbs[i]);
     return 0;
 }
@@ -5021,7 +5530,7 @@ SlotKit_clear_(PyObject *self_)
     Py_CLEAR(k->k_observed);
     Py_CLEAR(k->k_busy_scope);
     Py_CLEAR(k->k_idle_scope);
-    for (int i = 0; i < 4; i++)
+    for (int i = 0; i < KCB_N; i++)
         Py_CLEAR(k->k_cbs[i]);
     return 0;
 }
@@ -5041,10 +5550,11 @@ SlotKit_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
     (void)kwds;
     if (!PyArg_ParseTuple(args, "OO", &slot, &smgr))
         return NULL;
-    if (!PyObject_TypeCheck(slot, &FSMType) ||
+    if (!PyObject_TypeCheck(slot, &SlotBaseType) ||
         !PyObject_TypeCheck(smgr, &FSMType)) {
         PyErr_SetString(PyExc_TypeError,
-                        "SlotKit(slot, smgr): native FSMs required");
+                        "SlotKit(slot, smgr): a SlotBase and a native "
+                        "FSM required");
         return NULL;
     }
     SlotKit *k = PyObject_GC_New(SlotKit, type);
@@ -5057,10 +5567,10 @@ SlotKit_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
     k->k_observed = NULL;
     k->k_busy_scope = NULL;
     k->k_idle_scope = NULL;
-    for (int i = 0; i < 4; i++)
+    for (int i = 0; i < KCB_N; i++)
         k->k_cbs[i] = NULL;
     PyObject_GC_Track((PyObject *)k);
-    for (int i = 0; i < 4; i++) {
+    for (int i = 0; i < KCB_N; i++) {
         KitCb *cb = PyObject_GC_New(KitCb, &KitCbType);
         if (cb == NULL) {
             Py_DECREF((PyObject *)k);
@@ -5089,6 +5599,9 @@ slotkit_types_init(void)
     KitCbType.tp_flags = Py_TPFLAGS_DEFAULT | Py_TPFLAGS_HAVE_GC;
     KitCbType.tp_traverse = KitCb_traverse;
     KitCbType.tp_clear = KitCb_clear_;
+    /* all of the kit's callbacks are the library's own: they answer
+     * _cueball_internal like _ConnErrCb, whose job one of them does */
+    KitCbType.tp_getset = ConnErrCb_getset;
 
     SlotKitType.tp_dealloc = SlotKit_dealloc;
     SlotKitType.tp_flags = Py_TPFLAGS_DEFAULT | Py_TPFLAGS_HAVE_GC;
@@ -5122,6 +5635,9 @@ PyMethodDef speed_methods[] = {
      (PyCFunction)(void (*)(void))speed_set_claim_helpers, METH_FASTCALL,
      NULL},
     {"_set_tracer", speed_set_tracer, METH_O, NULL},
+    {"_set_stack_traces",
+     (PyCFunction)(void (*)(void))speed_set_stack_traces, METH_FASTCALL,
+     NULL},
     {"count_listeners",
      (PyCFunction)(void (*)(void))speed_count_listeners, METH_FASTCALL,
      NULL},
@@ -5196,7 +5712,9 @@ PyInit__speed(void)
     s_p_busy_hwm = PyUnicode_InternFromString("p_busy_hwm");
     s_p_demand_hwm = PyUnicode_InternFromString("p_demand_hwm");
     s_ticket_slow = PyUnicode_InternFromString("_ticket_slow");
-    s_ch_waiter_node = PyUnicode_InternFromString("ch_waiter_node");
+    s_p_idleq = PyUnicode_InternFromString("p_idleq");
+    s_p_waiters = PyUnicode_InternFromString("p_waiters");
+    s_p_initq = PyUnicode_InternFromString("p_initq");
     s_p_counters = PyUnicode_InternFromString("p_counters");
     s_p_rebal_scheduled = PyUnicode_InternFromString("p_rebal_scheduled");
     s_max_claim_queue = PyUnicode_InternFromString("max-claim-queue");
@@ -5209,10 +5727,6 @@ PyInit__speed(void)
     s_connecting_st = PyUnicode_InternFromString("connecting");
     s_killing_st = PyUnicode_InternFromString("killing");
     s_unwanted_evt = PyUnicode_InternFromString("unwanted");
-    s_csf_handle = PyUnicode_InternFromString("csf_handle");
-    s_csf_prev_handle = PyUnicode_InternFromString("csf_prev_handle");
-    s_csf_wanted = PyUnicode_InternFromString("csf_wanted");
-    s_csf_monitor = PyUnicode_InternFromString("csf_monitor");
     s_sm_socket = PyUnicode_InternFromString("sm_socket");
     t_busy_valid = PyTuple_Pack(6, s_idle, s_stopping_st, s_stopped_st,
                                 s_retrying_st, s_killing_st,
@@ -5221,7 +5735,6 @@ PyInit__speed(void)
                                 s_stopping_st, s_stopped_st, s_busy_st);
     s_p_backends = PyUnicode_InternFromString("p_backends");
     s_p_dead = PyUnicode_InternFromString("p_dead");
-    s_p_initq_node = PyUnicode_InternFromString("p_initq_node");
     s_connected_to_backend =
         PyUnicode_InternFromString("connectedToBackend");
     s_slot_state_changed =
@@ -5248,6 +5761,7 @@ PyInit__speed(void)
         PyType_Ready(&FailCbType) < 0 ||
         PyType_Ready(&CHType) < 0 ||
         PyType_Ready(&FSMType) < 0 ||
+        PyType_Ready(&SlotBaseType) < 0 ||
         PyType_Ready(&QNodeType) < 0 ||
         PyType_Ready(&NQueueType) < 0 ||
         PyType_Ready(&CTType) < 0 ||
@@ -5262,6 +5776,11 @@ PyInit__speed(void)
     if (g_remove_desc == NULL)
         return NULL;
     Py_INCREF(g_remove_desc);
+    if (ch_entries_init() < 0)
+        return NULL;
+    g_inf = PyFloat_FromDouble(HUGE_VAL);
+    if (g_inf == NULL)
+        return NULL;
 
     PyObject *m = PyModule_Create(&speedmodule);
     if (m == NULL)
@@ -5272,6 +5791,8 @@ PyInit__speed(void)
     PyModule_AddObject(m, "StateScope", (PyObject *)&ScopeType);
     Py_INCREF(&FSMType);
     PyModule_AddObject(m, "FSM", (PyObject *)&FSMType);
+    Py_INCREF(&SlotBaseType);
+    PyModule_AddObject(m, "SlotBase", (PyObject *)&SlotBaseType);
     Py_INCREF(&CHType);
     PyModule_AddObject(m, "ClaimHandleBase", (PyObject *)&CHType);
     Py_INCREF(&NQueueType);

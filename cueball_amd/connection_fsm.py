@@ -49,12 +49,19 @@ try:
     if _os.environ.get("CUEBALL_PURE"):
         _native_count = None
         _SlotKit = None
+        _SlotFSMBase = FSM
     else:
         from ._speed import count_listeners as _native_count
         from ._speed import SlotKit as _SlotKit
+        # the slot fields of the claim cycle (csf_handle,
+        # csf_prev_handle, csf_wanted, csf_monitor, p_idleq_node,
+        # p_initq_node) are members of this native FSM subtype; the
+        # pure runtime keeps them as plain attributes
+        from ._speed import SlotBase as _SlotFSMBase
 except ImportError:
     _native_count = None
     _SlotKit = None
+    _SlotFSMBase = FSM
 
 
 def _call_optional(obj: Any, *names: str) -> None:
@@ -656,6 +663,8 @@ if _native_count is not None:
         mod_errors.ClaimHandleMisusedError,
         mod_utils.maybe_capture_stack_trace,
     )
+    # the core skips that call while stack traces are off
+    mod_utils._bind_native_stack_flag(_speed_mod._set_stack_traces)
 
     class ClaimHandle(_CHBase):  # noqa: F811
         """Claim handle backed by the native core (docs: PyClaimHandle)."""
@@ -721,7 +730,7 @@ def count_listeners(emitter: Any, event: str) -> int:
     return n
 
 
-class ConnectionSlotFSM(FSM):
+class ConnectionSlotFSM(_SlotFSMBase):
     """One pool/set slot: drives a SocketMgrFSM and reports the
     transitions its owner cares about (lib/connection-fsm.js:810-1242)."""
 

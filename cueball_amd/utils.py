@@ -63,14 +63,29 @@ def stack_traces_enabled() -> bool:
     return _STACK_TRACES_ENABLED
 
 
+#: the native core's mirror of the flag (set by connection_fsm when the
+#: core is loaded): fn(enabled, placeholder)
+_native_stack_flag = None
+
+
+def _bind_native_stack_flag(fn) -> None:
+    global _native_stack_flag
+    _native_stack_flag = fn
+    fn(_STACK_TRACES_ENABLED, _DISABLED_STACK)
+
+
 def enable_stack_traces() -> None:
     global _STACK_TRACES_ENABLED
     _STACK_TRACES_ENABLED = True
+    if _native_stack_flag is not None:
+        _native_stack_flag(True, _DISABLED_STACK)
 
 
 def disable_stack_traces() -> None:
     global _STACK_TRACES_ENABLED
     _STACK_TRACES_ENABLED = False
+    if _native_stack_flag is not None:
+        _native_stack_flag(False, _DISABLED_STACK)
 
 
 _DISABLED_STACK = [

@@ -225,7 +225,7 @@ def main():
                     help="compare bench.py of this tree with the tree in "
                          "DIR, the option off in both")
     ap.add_argument("--config", default="headline",
-                    choices=("headline", "agent"),
+                    choices=("headline", "static1", "codel", "agent"),
                     help="the bench.py scenario of --against")
     args = ap.parse_args()
 
