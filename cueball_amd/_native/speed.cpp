@@ -27,6 +27,33 @@
 
 #include "lathist.h"
 
+/* The library's own listeners of the claim cycle are intrinsic hooks of
+ * the core (profiles/claim_cycle_intrinsic.md).  Each part can be
+ * switched back on its own at build time, e.g.
+ * CFLAGS=-DCUEBALL_HANDLE_HOOKS=0, for the leave-one-out measurements:
+ *   CUEBALL_HANDLE_HOOKS  the ticket and the busy slot's reaction to
+ *                         released/closed are fields of the handle
+ *   CUEBALL_SLOT_HOOKS    the slot kit's smgr/unwanted listeners of the
+ *                         busy and idle states are hooks of the emission
+ *   CUEBALL_LAZY_SCOPES   a transition's scope is made when first asked for
+ *   CUEBALL_VECTORCALL    the core's own callables take vectorcall, and
+ *                         ConnectionPool.claim has a native entry */
+#ifndef CUEBALL_HANDLE_HOOKS
+#define CUEBALL_HANDLE_HOOKS 1
+#endif
+#ifndef CUEBALL_SLOT_HOOKS
+#define CUEBALL_SLOT_HOOKS 1
+#endif
+#ifndef CUEBALL_LAZY_SCOPES
+#define CUEBALL_LAZY_SCOPES 1
+#endif
+#ifndef CUEBALL_VECTORCALL
+#define CUEBALL_VECTORCALL 1
+#endif
+#if !defined(Py_TPFLAGS_HAVE_VECTORCALL) && defined(_Py_TPFLAGS_HAVE_VECTORCALL)
+#define Py_TPFLAGS_HAVE_VECTORCALL _Py_TPFLAGS_HAVE_VECTORCALL
+#endif
+
 namespace {
 
 /* interned strings, created at module init */
@@ -326,23 +353,18 @@ Emitter_once(PyObject *self_, PyObject *const *args, Py_ssize_t nargs)
     return (PyObject *)w;
 }
 
-PyObject *
-Emitter_remove_listener(PyObject *self_, PyObject *const *args,
-                        Py_ssize_t nargs)
+/* remove one registration; *found_at is its index before the removal,
+ * or -1 if there was none */
+int
+emitter_remove_core(Emitter *self, PyObject *const *args,
+                    Py_ssize_t *found_at)
 {
-    Emitter *self = (Emitter *)self_;
-    if (nargs != 2) {
-        PyErr_SetString(PyExc_TypeError, "remove_listener(event, listener)");
-        return NULL;
-    }
+    *found_at = -1;
     if (self->ev_events == NULL)
-        Py_RETURN_NONE;
+        return 0;
     PyObject *ls = PyDict_GetItemWithError(self->ev_events, args[0]);
-    if (ls == NULL) {
-        if (PyErr_Occurred())
-            return NULL;
-        Py_RETURN_NONE;
-    }
+    if (ls == NULL)
+        return PyErr_Occurred() ? -1 : 0;
     Py_ssize_t n = PyList_GET_SIZE(ls);
     Py_ssize_t found = -1;
     for (Py_ssize_t i = 0; i < n; i++) {
@@ -356,7 +378,7 @@ Emitter_remove_listener(PyObject *self_, PyObject *const *args,
          * implementation) */
         int eq = PyObject_RichCompareBool(item, args[1], Py_EQ);
         if (eq < 0)
-            return NULL;
+            return -1;
         if (eq) {
             found = i;
             break;
@@ -375,7 +397,7 @@ Emitter_remove_listener(PyObject *self_, PyObject *const *args,
             }
             int eq = PyObject_RichCompareBool(inner, args[1], Py_EQ);
             if (eq < 0)
-                return NULL;
+                return -1;
             if (eq) {
                 found = i;
                 break;
@@ -390,8 +412,23 @@ Emitter_remove_listener(PyObject *self_, PyObject *const *args,
          * (and its key) every cycle.  Everything that reports events
          * treats an empty list as absent. */
         if (list_remove_at_keep(ls, found) < 0)
-            return NULL;
+            return -1;
+        *found_at = found;
     }
+    return 0;
+}
+
+PyObject *
+Emitter_remove_listener(PyObject *self_, PyObject *const *args,
+                        Py_ssize_t nargs)
+{
+    if (nargs != 2) {
+        PyErr_SetString(PyExc_TypeError, "remove_listener(event, listener)");
+        return NULL;
+    }
+    Py_ssize_t at;
+    if (emitter_remove_core((Emitter *)self_, args, &at) < 0)
+        return NULL;
     Py_RETURN_NONE;
 }
 
@@ -595,8 +632,9 @@ typedef struct {
 
 extern PyTypeObject ScopeType;
 
-/* Freed scopes are kept for the next transition (one is made per
- * transition, six per claim cycle). */
+/* Freed scopes are kept for the next state that asks for one (see
+ * fsm_need_scope; of the six states of a claim cycle only the handle's
+ * `claimed` does). */
 #define SCOPE_FREELIST_MAX 32
 Scope *scope_freelist[SCOPE_FREELIST_MAX];
 int scope_freelist_n = 0;
@@ -854,6 +892,11 @@ Scope_goto_state(PyObject *self_, PyObject *state)
     Py_RETURN_NONE;
 }
 
+/* the claim handle's own remove_listener (ClaimHandleBase section) */
+PyObject *g_ch_remove_desc;
+PyObject *CH_remove_listener(PyObject *self_, PyObject *const *args,
+                             Py_ssize_t nargs);
+
 /* undo one S.on() registration */
 int
 scope_unregister(PyObject *em, PyObject *evt, PyObject *cb)
@@ -864,11 +907,13 @@ scope_unregister(PyObject *em, PyObject *evt, PyObject *cb)
     int fast = 0;
     if (PyType_IsSubtype(Py_TYPE(em), &EmitterType)) {
         PyObject *desc = _PyType_Lookup(Py_TYPE(em), s_remove_listener);
-        fast = (desc == g_remove_desc);
+        fast = (desc == g_remove_desc) ? 1
+            : (desc != NULL && desc == g_ch_remove_desc) ? 2 : 0;
     }
     if (fast) {
         PyObject *cargs[2] = {evt, cb};
-        r = Emitter_remove_listener(em, cargs, 2);
+        r = fast == 1 ? Emitter_remove_listener(em, cargs, 2)
+                      : CH_remove_listener(em, cargs, 2);
     } else {
         r = PyObject_CallMethodObjArgs(em, s_remove_listener, evt, cb,
                                        NULL);
@@ -1043,6 +1088,9 @@ struct FSMOb {
     PyObject *f_flush_bound;    /* cached bound _flush_state_changed */
     PyObject *f_fastkit;        /* SlotKit* or NULL: native entries for
                                  * the busy/idle hot cycle */
+    PyObject *f_watchkit;       /* SlotKit* or NULL, on a socket manager:
+                                 * the kit whose slot reacts to this
+                                 * FSM's stateChanged while busy or idle */
     int f_entering;
     int f_emit_scheduled;
 };
@@ -1050,8 +1098,26 @@ struct FSMOb {
 /* forward decl (SlotKit lives after the CH/Queue sections);
  * returns 1 = state entered natively, 0 = use the python entry,
  * -1 = error */
-int slotkit_maybe_entry(PyObject *kit_, FSMOb *fsm, PyObject *target,
-                        Scope *scope);
+int slotkit_maybe_entry(PyObject *kit_, FSMOb *fsm, PyObject *target);
+/* the watching kit's reaction to a stateChanged of its socket manager,
+ * after the listeners in the list */
+int slotkit_smgr_hook(PyObject *kit_, PyObject *st, unsigned long serial);
+/* the kit's slot's transition count: taken before an emission, it tells
+ * the hook afterwards whether the slot was in its state all along (a
+ * listener registered during an emission is not called by it either) */
+unsigned long slotkit_slot_serial(PyObject *kit_);
+/* stateChanged of a claim handle: ticket hook, listeners, slot hook */
+int ch_emit_state_changed(FSMOb *self, PyObject *st);
+
+/* The scope of the current state, made on first use: most states of the
+ * claim cycle register nothing.  Borrowed; NULL on error. */
+static inline Scope *
+fsm_need_scope(FSMOb *self)
+{
+    if (self->f_scope == NULL)
+        self->f_scope = (PyObject *)scope_new((PyObject *)self);
+    return (Scope *)self->f_scope;
+}
 
 /* claim-handle terminal cleanup (defined near the CH section) */
 extern PyObject *t_empty;
@@ -1150,14 +1216,25 @@ fsm_flush_core(FSMOb *self)
 {
     self->f_emit_scheduled = 0;
     int n = 0;
+    int is_handle = PyObject_TypeCheck((PyObject *)self, &CHType);
     while (self->f_eq_head < self->f_eq_len && n++ < FSM_FLUSH_CAP) {
         /* pop by index; listeners may queue more (or flush again)
          * while they run, so the queue is read afresh every turn */
         PyObject *st = self->f_eq[self->f_eq_head++];
         if (self->f_eq_head == self->f_eq_len)
             self->f_eq_head = self->f_eq_len = 0;
-        PyObject *eargs[2] = {s_stateChanged, st};
-        int r = emitter_emit_core(&self->base, eargs[0], eargs + 1, 1);
+        int r;
+        if (is_handle) {
+            r = ch_emit_state_changed(self, st);
+        } else {
+            PyObject *eargs[2] = {s_stateChanged, st};
+            unsigned long serial = self->f_watchkit == NULL ? 0
+                : slotkit_slot_serial(self->f_watchkit);
+            r = emitter_emit_core(&self->base, eargs[0], eargs + 1, 1);
+            if (r >= 0 && serial != 0 && self->f_watchkit != NULL &&
+                slotkit_smgr_hook(self->f_watchkit, st, serial) < 0)
+                r = -1;
+        }
         Py_DECREF(st);
         if (r < 0) {
             fsm_eq_compact(self);
@@ -1198,6 +1275,7 @@ typedef struct {
     PyObject *fb_loop;
     PyObject *fb_list;   /* list of FSMOb */
     Py_ssize_t fb_pos;   /* next index to drain */
+    vectorcallfunc fb_vectorcall;
 } FlushBatch;
 
 extern PyTypeObject FlushBatchType;
@@ -1212,11 +1290,10 @@ flushbatch_detach(FlushBatch *self)
         PyErr_Clear();
 }
 
-PyObject *
-FlushBatch_call(PyObject *self_, PyObject *args, PyObject *kwds)
+static PyObject *
+flushbatch_run(PyObject *self_)
 {
     FlushBatch *self = (FlushBatch *)self_;
-    (void)args; (void)kwds;
     int rounds = 0;
     while (self->fb_pos < PyList_GET_SIZE(self->fb_list) &&
            rounds < FLUSH_DRAIN_CAP) {
@@ -1259,6 +1336,22 @@ FlushBatch_call(PyObject *self_, PyObject *args, PyObject *kwds)
     Py_RETURN_NONE;
 }
 
+PyObject *
+FlushBatch_call(PyObject *self_, PyObject *args, PyObject *kwds)
+{
+    (void)args; (void)kwds;
+    return flushbatch_run(self_);
+}
+
+/* the event loop calls the batch with no arguments: no tuple is built */
+static PyObject *
+FlushBatch_vectorcall(PyObject *self_, PyObject *const *args, size_t nargsf,
+                      PyObject *kwnames)
+{
+    (void)args; (void)nargsf; (void)kwnames;
+    return flushbatch_run(self_);
+}
+
 int
 FlushBatch_traverse(PyObject *self_, visitproc visit, void *arg)
 {
@@ -1292,7 +1385,7 @@ PyTypeObject FlushBatchType = {
     0,
     FlushBatch_dealloc,
     0, 0, 0, 0, 0, 0, 0, 0, 0,
-    FlushBatch_call,
+    FlushBatch_call,              /* vectorcall: see slotkit_types_init */
     0, 0, 0, 0,
     Py_TPFLAGS_DEFAULT | Py_TPFLAGS_HAVE_GC,
     0,
@@ -1324,6 +1417,7 @@ fsm_schedule_flush(FSMOb *self)
         Py_INCREF(self->f_loop);
         fb->fb_loop = self->f_loop;
         fb->fb_pos = 0;
+        fb->fb_vectorcall = FlushBatch_vectorcall;
         fb->fb_list = PyList_New(0);
         PyObject_GC_Track((PyObject *)fb);
         if (fb->fb_list == NULL) {
@@ -1421,33 +1515,31 @@ fsm_enter_loop(FSMOb *self, PyObject *state)
         Py_INCREF(target);
         Py_XSETREF(self->f_hist[self->f_hist_n % FSM_HISTORY], target);
         self->f_hist_n++;
-        Scope *scope = scope_new((PyObject *)self);
-        if (scope == NULL) {
+#if !CUEBALL_LAZY_SCOPES
+        if (fsm_need_scope(self) == NULL) {
             Py_DECREF(target);
             return -1;
         }
-        Py_INCREF((PyObject *)scope);
-        Py_XSETREF(self->f_scope, (PyObject *)scope);
+#endif
 
         if (g_tracer != NULL && g_tracer != Py_None) {
             PyObject *targs[2] = {(PyObject *)self, target};
             PyObject *tr = PyObject_Vectorcall(g_tracer, targs, 2, NULL);
             if (tr == NULL) {
-                Py_DECREF(scope);
                 Py_DECREF(target);
                 return -1;
             }
             Py_DECREF(tr);
         }
 
+        /* The native entries take the state's scope from fsm_need_scope()
+         * if they register anything; a Python entry is handed one. */
         int handled = 0;
         if (self->f_fastkit != NULL) {
             self->f_entering = 1;
-            handled = slotkit_maybe_entry(self->f_fastkit, self, target,
-                                          scope);
+            handled = slotkit_maybe_entry(self->f_fastkit, self, target);
             self->f_entering = 0;
             if (handled < 0) {
-                Py_DECREF(scope);
                 Py_DECREF(target);
                 return -1;
             }
@@ -1455,20 +1547,17 @@ fsm_enter_loop(FSMOb *self, PyObject *state)
         PyObject *r;
         ch_entry_fn direct = handled ? NULL : ch_direct_entry(self, target);
         if (handled) {
-            Py_DECREF(scope);
             r = Py_None;
             Py_INCREF(r);
         } else if (direct != NULL) {
             /* the type's entry for this state is this module's own C
              * function: call it without building a bound method */
             self->f_entering = 1;
-            r = direct((PyObject *)self, (PyObject *)scope);
-            Py_DECREF(scope);
+            r = direct((PyObject *)self, NULL);
             self->f_entering = 0;
         } else {
             PyObject *attr = entry_attr_name(target);
             if (attr == NULL) {
-                Py_DECREF(scope);
                 Py_DECREF(target);
                 return -1;
             }
@@ -1479,13 +1568,18 @@ fsm_enter_loop(FSMOb *self, PyObject *state)
                 PyErr_Format(g_fsm_error,
                              "%s has no state-entry function for %R",
                              Py_TYPE(self)->tp_name, target);
-                Py_DECREF(scope);
                 Py_DECREF(target);
                 return -1;
             }
-
+            PyObject *scope = (PyObject *)fsm_need_scope(self);
+            if (scope == NULL) {
+                Py_DECREF(entry);
+                Py_DECREF(target);
+                return -1;
+            }
+            Py_INCREF(scope);
             self->f_entering = 1;
-            r = PyObject_CallOneArg(entry, (PyObject *)scope);
+            r = PyObject_CallOneArg(entry, scope);
             Py_DECREF(entry);
             Py_DECREF(scope);
             self->f_entering = 0;
@@ -1850,6 +1944,7 @@ FSM_traverse(PyObject *self_, visitproc visit, void *arg)
         Py_VISIT(self->f_hist[i]);
     Py_VISIT(self->f_flush_bound);
     Py_VISIT(self->f_fastkit);
+    Py_VISIT(self->f_watchkit);
     return Emitter_traverse(self_, visit, arg);
 }
 
@@ -1868,6 +1963,7 @@ FSM_clear_(PyObject *self_)
     self->f_hist_n = 0;
     Py_CLEAR(self->f_flush_bound);
     Py_CLEAR(self->f_fastkit);
+    Py_CLEAR(self->f_watchkit);
     return Emitter_clear_(self_);
 }
 
@@ -2500,6 +2596,20 @@ typedef struct {
     int chb_leak_check;
     int chb_pinger;
     int chb_lat_open;       /* wait recorded, hold still running */
+    /* The library's own two listeners of a handle are not list entries.
+     * The ticket: while chb_tk_on, every return to "waiting" runs the
+     * pool's idle-queue handoff before any listener is called; the
+     * three queues are the pool's (Queue objects, owned). */
+    PyObject *chb_idleq, *chb_waiters, *chb_initq;
+    int chb_tk_on;
+    int chb_tk_err_on_empty;
+    /* The busy slot: armed by the slot kit's busy entry with the slot's
+     * transition count at that entry (0 = not armed) and the number of
+     * stateChanged listeners the handle had then.  On released/closed
+     * the slot reacts after that many listeners and before the later
+     * ones, and only while it still is in that same busy state. */
+    unsigned long chb_bk_serial;
+    Py_ssize_t chb_bk_pos;
 } CHOb;
 
 extern PyTypeObject CHType;
@@ -2990,7 +3100,12 @@ CH_state_waiting(PyObject *self_, PyObject *scope)
     Py_INCREF(t_waiting_valid);
     Py_XSETREF(self->base.f_valid, t_waiting_valid);
     Py_CLEAR(self->chb_slot);
+    self->chb_bk_serial = 0;
     if (isfinite(self->chb_claim_timeout)) {
+        if (scope == NULL)
+            scope = (PyObject *)fsm_need_scope(&self->base);
+        if (scope == NULL)
+            return NULL;
         PyObject *ms = PyFloat_FromDouble(self->chb_claim_timeout);
         if (ms == NULL)
             return NULL;
@@ -3081,6 +3196,12 @@ CH_state_claimed(PyObject *self_, PyObject *scope)
         nec->ce_handle = self_;
         PyObject_GC_Track((PyObject *)nec);
         ec = (PyObject *)nec;
+    }
+    if (scope == NULL)
+        scope = (PyObject *)fsm_need_scope(&self->base);
+    if (scope == NULL) {
+        Py_DECREF(ec);
+        return NULL;
     }
     PyObject *args[3] = {conn, s_error_evt, ec};
     PyObject *r = Scope_on(scope, args, 3);
@@ -3261,6 +3382,36 @@ CH_once(PyObject *self_, PyObject *const *args, Py_ssize_t nargs)
     return Emitter_once(self_, args, nargs);
 }
 
+/* Removing a listener that sits before the busy slot's place in the
+ * order moves that place with it. */
+PyObject *
+CH_remove_listener(PyObject *self_, PyObject *const *args, Py_ssize_t nargs)
+{
+    CHOb *self = (CHOb *)self_;
+    if (nargs != 2) {
+        PyErr_SetString(PyExc_TypeError, "remove_listener(event, listener)");
+        return NULL;
+    }
+    Py_ssize_t at;
+    if (emitter_remove_core(&self->base.base, args, &at) < 0)
+        return NULL;
+    if (at >= 0 && at < self->chb_bk_pos &&
+        (args[0] == s_stateChanged ||
+         (PyUnicode_Check(args[0]) &&
+          PyUnicode_Compare(args[0], s_stateChanged) == 0)))
+        self->chb_bk_pos--;
+    Py_RETURN_NONE;
+}
+
+PyObject *
+CH_remove_all_listeners(PyObject *self_, PyObject *const *args,
+                        Py_ssize_t nargs)
+{
+    /* whatever is registered from here on comes after the slot */
+    ((CHOb *)self_)->chb_bk_pos = 0;
+    return Emitter_remove_all_listeners(self_, args, nargs);
+}
+
 /* -- init / gc ------------------------------------------------------------ */
 
 int
@@ -3277,6 +3428,9 @@ CH_traverse(PyObject *self_, visitproc visit, void *arg)
     Py_VISIT(self->chb_last_error);
     Py_VISIT(self->chb_waiter_node);
     Py_VISIT((PyObject *)self->chb_lat);
+    Py_VISIT(self->chb_idleq);
+    Py_VISIT(self->chb_waiters);
+    Py_VISIT(self->chb_initq);
     return FSM_traverse(self_, visit, arg);
 }
 
@@ -3294,6 +3448,9 @@ CH_clear_(PyObject *self_)
     Py_CLEAR(self->chb_last_error);
     Py_CLEAR(self->chb_waiter_node);
     Py_CLEAR(self->chb_lat);
+    Py_CLEAR(self->chb_idleq);
+    Py_CLEAR(self->chb_waiters);
+    Py_CLEAR(self->chb_initq);
     return FSM_clear_(self_);
 }
 
@@ -3349,8 +3506,13 @@ CH__setup(PyObject *self_, PyObject *const *args, Py_ssize_t nargs)
     if (resolved == NULL)
         return NULL;
     Py_XSETREF(self->base.f_loop, resolved);
+#if !CUEBALL_HANDLE_HOOKS
+    /* with the hooks the event dict appears with the first on()/once() */
     if (Emitter_init(self_, NULL, NULL) < 0)
         return NULL;
+#endif
+    self->chb_tk_on = 0;
+    self->chb_bk_serial = 0;
     if (fsm_goto_state(&self->base, s_waiting) < 0)
         return NULL;
     if (self->chb_lat != NULL && self->chb_lat->pl_direct &&
@@ -3389,6 +3551,11 @@ PyMethodDef CH_methods[] = {
      METH_NOARGS, NULL},
     {"on", (PyCFunction)(void (*)(void))CH_on, METH_FASTCALL, NULL},
     {"once", (PyCFunction)(void (*)(void))CH_once, METH_FASTCALL, NULL},
+    {"remove_listener", (PyCFunction)(void (*)(void))CH_remove_listener,
+     METH_FASTCALL, NULL},
+    {"remove_all_listeners",
+     (PyCFunction)(void (*)(void))CH_remove_all_listeners, METH_FASTCALL,
+     NULL},
     {"state_waiting", CH_state_waiting, METH_O, NULL},
     {"state_claiming", CH_state_claiming, METH_O, NULL},
     {"state_claimed", CH_state_claimed, METH_O, NULL},
@@ -4000,9 +4167,11 @@ queue_types_init(void)
 
 /* ------------------------------------------------------------------ */
 /* ClaimTicket: the pool's per-claim driver (pool.py _ClaimTicket) in  */
-/* C.  Registered as the claim handle's stateChanged listener; on      */
-/* every return to "waiting" it scans the idle queue and performs the  */
-/* try_ handoff without entering Python.  Anything off the hot path    */
+/* C.  On every return of the handle to "waiting" it scans the idle    */
+/* queue and performs the try_ handoff without entering Python.  On    */
+/* the claim path it is no object: claim_fast switches it on as the    */
+/* handle's own first hook (ch_ticket_try_next); the ClaimTicket type  */
+/* is the same code as a stateChanged listener.  Anything off the hot  */
 /* (pool not running, idle queue empty, errorOnEmpty) delegates to     */
 /* pool._ticket_slow, which holds the full reference logic.            */
 
@@ -4016,14 +4185,20 @@ PyObject *s_p_idleq;         /* "p_idleq" */
 PyObject *s_p_waiters;       /* "p_waiters" */
 PyObject *s_p_initq;         /* "p_initq" */
 
+/* what the handoff works on: the fields of a ClaimTicket object, or a
+ * view of the claim handle's own ticket fields (ch_ticket_try_next) */
 typedef struct {
-    PyObject_HEAD
     PyObject *ct_pool;
     PyObject *ct_handle;     /* a CHOb */
     NQueue *ct_idleq;        /* owned; NULL => always delegate */
     NQueue *ct_waiters;      /* owned */
     NQueue *ct_initq;        /* owned */
     int ct_err_on_empty;
+} TicketCore;
+
+typedef struct {
+    PyObject_HEAD
+    TicketCore core;
 } CTOb;
 
 extern PyTypeObject CTType;
@@ -4032,7 +4207,7 @@ extern PyTypeObject CTType;
  * the native deque leaves them NULL and the ticket permanently
  * delegates to the python slow path */
 static void
-ct_bind_queues(CTOb *t, PyObject *pool)
+ct_bind_queues(TicketCore *t, PyObject *pool)
 {
     PyObject *iq = PyObject_GetAttr(pool, s_p_idleq);
     PyObject *wq = iq ? PyObject_GetAttr(pool, s_p_waiters) : NULL;
@@ -4057,7 +4232,7 @@ ct_bind_queues(CTOb *t, PyObject *pool)
 }
 
 static int
-ct_note_demand(CTOb *t)
+ct_note_demand(TicketCore *t)
 {
     /* O(1) inline of pool._note_demand() */
     Py_ssize_t nw = t->ct_waiters->q_len;
@@ -4124,7 +4299,7 @@ extern PyObject *s_rebalance;    /* "rebalance" (SlotDispatch section) */
  * handle, fold the demand sample, bump the HWM/queued counters, and
  * schedule a rebalance unless one is already pending */
 static int
-ct_enqueue_waiter(CTOb *t)
+ct_enqueue_waiter(TicketCore *t)
 {
     QNode *n = nqueue_push(t->ct_waiters, t->ct_handle);
     if (n == NULL)
@@ -4212,7 +4387,7 @@ ct_enqueue_waiter(CTOb *t)
 }
 
 static int
-ct_slow(CTOb *t)
+ct_slow(TicketCore *t)
 {
     PyObject *r = PyObject_CallMethodObjArgs(
         t->ct_pool, s_ticket_slow, t->ct_handle,
@@ -4224,7 +4399,7 @@ ct_slow(CTOb *t)
 }
 
 static int
-ct_try_next(CTOb *t)
+ct_try_next(TicketCore *t)
 {
     CHOb *h = (CHOb *)t->ct_handle;
     if (!ch_state_is(h, s_waiting))
@@ -4288,10 +4463,25 @@ ct_try_next(CTOb *t)
     return ct_slow(t);
 }
 
+/* the handle's own ticket: same handoff, on a view of its fields */
+static int
+ch_ticket_try_next(CHOb *h)
+{
+    TicketCore v = {h->chb_pool, (PyObject *)h, (NQueue *)h->chb_idleq,
+                    (NQueue *)h->chb_waiters, (NQueue *)h->chb_initq,
+                    h->chb_tk_err_on_empty};
+    /* the pool keeps its queues; the view borrows them and the pool */
+    PyObject *pool = v.ct_pool;
+    Py_INCREF(pool);
+    int r = ct_try_next(&v);
+    Py_DECREF(pool);
+    return r;
+}
+
 static PyObject *
 CT_call(PyObject *self_, PyObject *args, PyObject *kwds)
 {
-    CTOb *t = (CTOb *)self_;
+    TicketCore *t = &((CTOb *)self_)->core;
     (void)kwds;
     PyObject *st;
     if (PyTuple_GET_SIZE(args) != 1) {
@@ -4310,7 +4500,7 @@ CT_call(PyObject *self_, PyObject *args, PyObject *kwds)
 static int
 CT_traverse(PyObject *self_, visitproc visit, void *arg)
 {
-    CTOb *t = (CTOb *)self_;
+    TicketCore *t = &((CTOb *)self_)->core;
     Py_VISIT(t->ct_pool);
     Py_VISIT(t->ct_handle);
     Py_VISIT((PyObject *)t->ct_idleq);
@@ -4322,7 +4512,7 @@ CT_traverse(PyObject *self_, visitproc visit, void *arg)
 static int
 CT_clear_(PyObject *self_)
 {
-    CTOb *t = (CTOb *)self_;
+    TicketCore *t = &((CTOb *)self_)->core;
     Py_CLEAR(t->ct_pool);
     Py_CLEAR(t->ct_handle);
     Py_CLEAR(t->ct_idleq);
@@ -4355,9 +4545,10 @@ CT_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
                         "handle must be a ClaimHandleBase");
         return NULL;
     }
-    CTOb *t = PyObject_GC_New(CTOb, type);
-    if (t == NULL)
+    CTOb *tob = PyObject_GC_New(CTOb, type);
+    if (tob == NULL)
         return NULL;
+    TicketCore *t = &tob->core;
     Py_INCREF(pool);
     t->ct_pool = pool;
     Py_INCREF(handle);
@@ -4366,9 +4557,9 @@ CT_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
     t->ct_waiters = NULL;
     t->ct_initq = NULL;
     t->ct_err_on_empty = PyObject_IsTrue(err_on_empty);
-    PyObject_GC_Track((PyObject *)t);
+    PyObject_GC_Track((PyObject *)tob);
     ct_bind_queues(t, pool);
-    return (PyObject *)t;
+    return (PyObject *)tob;
 }
 
 PyTypeObject CTType = {
@@ -4455,7 +4646,8 @@ speed_pool_claim(PyObject *mod, PyObject *const *args, Py_ssize_t nargs)
  *            err_on_empty) -> handle
  * One C call for pool.claim's hot tail: allocate the ClaimHandle
  * subclass, run the _setup core (throw_error=True), build the native
- * ticket and register it as the stateChanged listener. */
+ * ticket's queues and switch the ticket on (with CUEBALL_HANDLE_HOOKS
+ * off: build a ClaimTicket and register it as stateChanged listener). */
 PyObject *CH__setup(PyObject *self_, PyObject *const *args,
                     Py_ssize_t nargs);
 
@@ -4497,11 +4689,26 @@ speed_claim_fast(PyObject *mod, PyObject *const *args, Py_ssize_t nargs)
     }
     Py_DECREF(r);
 
-    CTOb *t = PyObject_GC_New(CTOb, &CTType);
-    if (t == NULL) {
+#if CUEBALL_HANDLE_HOOKS
+    /* the ticket is the handle's own first hook: nothing is allocated
+     * and nothing registered */
+    {
+        CHOb *h = (CHOb *)handle;
+        TicketCore q = {NULL, NULL, NULL, NULL, NULL, 0};
+        ct_bind_queues(&q, pool);
+        Py_XSETREF(h->chb_idleq, (PyObject *)q.ct_idleq);
+        Py_XSETREF(h->chb_waiters, (PyObject *)q.ct_waiters);
+        Py_XSETREF(h->chb_initq, (PyObject *)q.ct_initq);
+        h->chb_tk_err_on_empty = err_on_empty;
+        h->chb_tk_on = 1;
+    }
+#else
+    CTOb *tob = PyObject_GC_New(CTOb, &CTType);
+    if (tob == NULL) {
         Py_DECREF(handle);
         return NULL;
     }
+    TicketCore *t = &tob->core;
     Py_INCREF(pool);
     t->ct_pool = pool;
     Py_INCREF(handle);
@@ -4510,15 +4717,16 @@ speed_claim_fast(PyObject *mod, PyObject *const *args, Py_ssize_t nargs)
     t->ct_waiters = NULL;
     t->ct_initq = NULL;
     t->ct_err_on_empty = err_on_empty;
-    PyObject_GC_Track((PyObject *)t);
+    PyObject_GC_Track((PyObject *)tob);
     ct_bind_queues(t, pool);
-    r = emitter_add((Emitter *)handle, s_stateChanged, (PyObject *)t);
-    Py_DECREF((PyObject *)t);
+    r = emitter_add((Emitter *)handle, s_stateChanged, (PyObject *)tob);
+    Py_DECREF((PyObject *)tob);
     if (r == NULL) {
         Py_DECREF(handle);
         return NULL;
     }
     Py_DECREF(r);
+#endif
     return handle;
 }
 
@@ -4534,8 +4742,9 @@ ct_type_init(void)
 }
 
 /* Terminal-state cycle breaker (see fsm_enter_loop): dispose the
- * terminal scope (fsm<->scope cycle) and unregister the pool ticket
- * from the handle's stateChanged listeners (handle<->ticket cycle).
+ * terminal scope (fsm<->scope cycle) and retire the pool ticket (with
+ * CUEBALL_HANDLE_HOOKS off: unregister it from the handle's
+ * stateChanged listeners, the handle<->ticket cycle).
  * Both are semantically invisible — the terminal scope registers
  * nothing, and the ticket only reacts to 'waiting', which is
  * unreachable from a terminal state.  User listeners are untouched
@@ -4563,6 +4772,11 @@ ch_terminal_cleanup(FSMOb *self)
         else
             Py_DECREF(r);
     }
+#if CUEBALL_HANDLE_HOOKS
+    /* "waiting" is unreachable from here: the ticket is done.  (A ticket
+     * registered as a listener, _AvoidClaimTicket, removes itself.) */
+    ((CHOb *)self)->chb_tk_on = 0;
+#else
     Emitter *em = &self->base;
     if (em->ev_events == NULL)
         return;
@@ -4581,20 +4795,22 @@ ch_terminal_cleanup(FSMOb *self)
             }
         }
     }
+#endif
 }
 
 /* ------------------------------------------------------------------ */
 /* SlotKit: native entries for ConnectionSlotFSM's busy/idle hot       */
 /* cycle (connection_fsm.py state_busy/state_idle).  One claim/release */
 /* runs idle -> busy -> idle; with the kit installed both entries and  */
-/* their event callbacks execute in C.  The kit's callbacks (the four  */
-/* listeners of the two states and the claimed handle's conn-error     */
-/* listener) are allocated once per slot, the four registrations of a  */
-/* cycle sit in their scopes' inline arrays, and the listener lists    */
-/* they go into keep their storage; what the slot's side of a cycle    */
-/* still allocates is its two scopes, taken from a freelist.  (The     */
-/* claim itself allocates a handle, a ticket and the handle's event    */
-/* dict and listener list.)  Installed only for slots without a health */
+/* their event reactions execute in C.  The four listeners of the two  */
+/* states are not registrations: the kit notes the slot's transition   */
+/* count at its busy and idle entries, and the emissions they listened */
+/* to (the socket manager's and the handle's stateChanged, the slot's  */
+/* own `unwanted`) call the kit while the slot still is in that very   */
+/* state.  Only the claimed handle's conn-error listener is a real     */
+/* registration (the leak detector and users look at that list), made  */
+/* with a callback allocated once per slot.  The slot's side of a      */
+/* cycle allocates nothing.  Installed only for slots without a health */
 /* checker;                                                            */
 /* monitor/unwanted idle entries fall back to the Python entry, and    */
 /* all exit transitions out of the cycle enter Python states.          */
@@ -4621,6 +4837,7 @@ typedef struct {
     PyObject_HEAD
     SlotKit *kc_kit;            /* owned */
     int kc_which;
+    vectorcallfunc kc_vectorcall;
 } KitCb;
 
 struct SlotKit {
@@ -4628,8 +4845,11 @@ struct SlotKit {
     FSMOb *k_slot;              /* owned */
     PyObject *k_smgr;           /* owned; an FSMOb */
     PyObject *k_observed;       /* event-observed smgr state, owned */
-    Scope *k_busy_scope;        /* owned; scope of the last busy entry */
-    Scope *k_idle_scope;        /* owned; scope of the last idle entry */
+    /* the slot's transition count (f_hist_n) at its last native busy
+     * and idle entry: a reaction belongs to that state only while the
+     * count still is what it was (0 = never entered) */
+    unsigned long k_busy_serial;
+    unsigned long k_idle_serial;
     PyObject *k_cbs[KCB_N];        /* owned KitCb instances */
 };
 
@@ -4650,28 +4870,28 @@ slotkit_conn_err_cb(PyObject *slot, PyObject *handle)
 }
 
 static int
-kit_scope_goto(Scope *scope, PyObject *state)
+kit_goto(SlotKit *k, unsigned long serial, PyObject *state)
 {
-    if (scope == NULL || !scope->sc_active)
+    if (serial == 0 || k->k_slot->f_hist_n != serial)
         return 0;  /* stale handler in the same cascade: obsolete */
-    return fsm_goto_state((FSMOb *)scope->sc_fsm, state);
+    return fsm_goto_state(k->k_slot, state);
 }
 
 static int
 kit_busy_on_release(SlotKit *k)
 {
-    Scope *S = k->k_busy_scope;
+    unsigned long S = k->k_busy_serial;
     PyObject *st = k->k_observed;
     int wanted = slot_field_true(&((SlotOb *)k->k_slot)->sl_wanted);
     if (wanted < 0)
         return -1;
     if (st == s_connected_st ||
         (st != NULL && PyUnicode_Compare(st, s_connected_st) == 0))
-        return kit_scope_goto(S, wanted ? s_idle : s_stopping_st);
+        return kit_goto(k, S, wanted ? s_idle : s_stopping_st);
     if (st == s_closed || PyUnicode_Compare(st, s_closed) == 0)
-        return kit_scope_goto(S, wanted ? s_connecting_st : s_stopped_st);
+        return kit_goto(k, S, wanted ? s_connecting_st : s_stopped_st);
     if (st == s_error_evt || PyUnicode_Compare(st, s_error_evt) == 0)
-        return kit_scope_goto(S, s_retrying_st);
+        return kit_goto(k, S, s_retrying_st);
     PyErr_Format(g_fsm_error,
                  "Handle released while smgr was in unhandled state %R",
                  st ? st : Py_None);
@@ -4681,25 +4901,25 @@ kit_busy_on_release(SlotKit *k)
 static int
 kit_busy_on_close(SlotKit *k)
 {
-    Scope *S = k->k_busy_scope;
+    unsigned long S = k->k_busy_serial;
     PyObject *st = k->k_observed;
     if (st == s_connected_st ||
         (st != NULL && PyUnicode_Compare(st, s_connected_st) == 0))
-        return kit_scope_goto(S, s_killing_st);
-    return kit_scope_goto(S, s_retrying_st);
+        return kit_goto(k, S, s_killing_st);
+    return kit_goto(k, S, s_retrying_st);
 }
 
 static int
 kit_idle_smgr_changed(SlotKit *k, PyObject *st)
 {
-    Scope *S = k->k_idle_scope;
+    unsigned long S = k->k_idle_serial;
     int wanted = slot_field_true(&((SlotOb *)k->k_slot)->sl_wanted);
     if (wanted < 0)
         return -1;
     if (st == s_error_evt || PyUnicode_Compare(st, s_error_evt) == 0)
-        return kit_scope_goto(S, wanted ? s_retrying_st : s_stopped_st);
+        return kit_goto(k, S, wanted ? s_retrying_st : s_stopped_st);
     if (st == s_closed || PyUnicode_Compare(st, s_closed) == 0)
-        return kit_scope_goto(S, wanted ? s_connecting_st : s_stopped_st);
+        return kit_goto(k, S, wanted ? s_connecting_st : s_stopped_st);
     PyErr_Format(g_fsm_error,
                  "Unhandled smgr state transition: connected => %R", st);
     return -1;
@@ -4709,27 +4929,23 @@ static int
 kit_idle_unwanted(SlotKit *k)
 {
     /* mirror of _idle_on_unwanted incl. the same-spin death fix */
-    Scope *S = k->k_idle_scope;
+    unsigned long S = k->k_idle_serial;
     PyObject *sst = ((FSMOb *)k->k_smgr)->f_state;
     if (sst == s_connected_st ||
         (sst != NULL && PyUnicode_Compare(sst, s_connected_st) == 0))
-        return kit_scope_goto(S, s_stopping_st);
+        return kit_goto(k, S, s_stopping_st);
     if (sst == s_error_evt || sst == s_closed ||
         (sst != NULL && (PyUnicode_Compare(sst, s_error_evt) == 0 ||
                          PyUnicode_Compare(sst, s_closed) == 0)))
-        return kit_scope_goto(S, s_stopped_st);
+        return kit_goto(k, S, s_stopped_st);
     return 0;
 }
 
 static PyObject *
-KitCb_call(PyObject *self_, PyObject *args, PyObject *kwds)
+kitcb_fire(PyObject *self_, PyObject *st)
 {
     KitCb *cb = (KitCb *)self_;
     SlotKit *k = cb->kc_kit;
-    PyObject *st = NULL;
-    (void)kwds;
-    if (PyTuple_GET_SIZE(args) >= 1)
-        st = PyTuple_GET_ITEM(args, 0);
     int r = 0;
     switch (cb->kc_which) {
     case KCB_BUSY_SMGR:
@@ -4773,6 +4989,23 @@ KitCb_call(PyObject *self_, PyObject *args, PyObject *kwds)
     Py_RETURN_NONE;
 }
 
+static PyObject *
+KitCb_call(PyObject *self_, PyObject *args, PyObject *kwds)
+{
+    (void)kwds;
+    return kitcb_fire(self_, PyTuple_GET_SIZE(args) >= 1
+                      ? PyTuple_GET_ITEM(args, 0) : NULL);
+}
+
+static PyObject *
+KitCb_vectorcall(PyObject *self_, PyObject *const *args, size_t nargsf,
+                 PyObject *kwnames)
+{
+    (void)kwnames;
+    return kitcb_fire(self_, PyVectorcall_NARGS(nargsf) >= 1 ? args[0]
+                                                             : NULL);
+}
+
 static int
 KitCb_traverse(PyObject *self_, visitproc visit, void *arg)
 {
@@ -4804,7 +5037,7 @@ PyTypeObject KitCbType = {
 /* -- the native state entries --------------------------------------- */
 
 static int
-kit_state_busy(SlotKit *k, Scope *scope)
+kit_state_busy(SlotKit *k)
 {
     FSMOb *slot = k->k_slot;
     Py_INCREF(t_busy_valid);
@@ -4816,15 +5049,45 @@ kit_state_busy(SlotKit *k, Scope *scope)
     Py_INCREF(hdl);
     Py_INCREF(s_connected_st);
     Py_XSETREF(k->k_observed, s_connected_st);
-    Py_INCREF((PyObject *)scope);
-    Py_XSETREF(k->k_busy_scope, scope);
+    k->k_busy_serial = slot->f_hist_n;
 
-    if (scope_on_c(scope, k->k_smgr, s_stateChanged,
-                   k->k_cbs[KCB_BUSY_SMGR]) < 0 ||
-        scope_on_c(scope, hdl, s_stateChanged,
-                   k->k_cbs[KCB_BUSY_HDL]) < 0) {
-        Py_DECREF(hdl);
-        return -1;
+#if !CUEBALL_SLOT_HOOKS
+    {
+        Scope *scope = fsm_need_scope(slot);
+        if (scope == NULL ||
+            scope_on_c(scope, k->k_smgr, s_stateChanged,
+                       k->k_cbs[KCB_BUSY_SMGR]) < 0) {
+            Py_DECREF(hdl);
+            return -1;
+        }
+    }
+#endif
+    int armed = 0;
+#if CUEBALL_HANDLE_HOOKS
+    if (PyObject_TypeCheck(hdl, &CHType)) {
+        /* the handle calls back by itself (ch_slot_hook), in the place
+         * a listener registered now would have */
+        CHOb *h = (CHOb *)hdl;
+        PyObject *ls = h->base.base.ev_events == NULL ? NULL :
+            PyDict_GetItemWithError(h->base.base.ev_events, s_stateChanged);
+        if (ls == NULL && PyErr_Occurred()) {
+            Py_DECREF(hdl);
+            return -1;
+        }
+        h->chb_bk_pos = (ls != NULL && PyList_Check(ls))
+            ? PyList_GET_SIZE(ls) : 0;
+        h->chb_bk_serial = k->k_busy_serial;
+        armed = 1;
+    }
+#endif
+    if (!armed) {
+        Scope *scope = fsm_need_scope(slot);
+        if (scope == NULL ||
+            scope_on_c(scope, hdl, s_stateChanged,
+                       k->k_cbs[KCB_BUSY_HDL]) < 0) {
+            Py_DECREF(hdl);
+            return -1;
+        }
     }
 
     PyObject *sst = ((FSMOb *)k->k_smgr)->f_state;
@@ -4860,7 +5123,7 @@ kit_state_busy(SlotKit *k, Scope *scope)
 }
 
 static int
-kit_state_idle(SlotKit *k, Scope *scope)
+kit_state_idle(SlotKit *k)
 {
     FSMOb *slot = k->k_slot;
     /* the monitor-conversion and unwanted cases keep the full Python
@@ -4878,8 +5141,7 @@ kit_state_idle(SlotKit *k, Scope *scope)
 
     Py_INCREF(t_idle_valid);
     Py_XSETREF(slot->f_valid, t_idle_valid);
-    Py_INCREF((PyObject *)scope);
-    Py_XSETREF(k->k_idle_scope, scope);
+    k->k_idle_serial = slot->f_hist_n;
 
     SlotOb *so = (SlotOb *)slot;
     if (slot_field_set(&so->sl_handle)) {
@@ -4892,18 +5154,22 @@ kit_state_idle(SlotKit *k, Scope *scope)
         Py_XDECREF(old_prev);
     }
 
+#if !CUEBALL_SLOT_HOOKS
+    Scope *scope = fsm_need_scope(slot);
+    if (scope == NULL)
+        return -1;
     if (scope_on_c(scope, k->k_smgr, s_stateChanged,
                    k->k_cbs[KCB_IDLE_SMGR]) < 0)
         return -1;
     if (scope_on_c(scope, (PyObject *)slot, s_unwanted_evt,
                    k->k_cbs[KCB_IDLE_UNWANTED]) < 0)
         return -1;
+#endif
     return 1;
 }
 
 int
-slotkit_maybe_entry(PyObject *kit_, FSMOb *fsm, PyObject *target,
-                    Scope *scope)
+slotkit_maybe_entry(PyObject *kit_, FSMOb *fsm, PyObject *target)
 {
     SlotKit *k = (SlotKit *)kit_;
     if (k->k_slot != fsm)
@@ -4911,13 +5177,206 @@ slotkit_maybe_entry(PyObject *kit_, FSMOb *fsm, PyObject *target,
     if (target == s_busy_st ||
         (PyUnicode_Check(target) &&
          PyUnicode_Compare(target, s_busy_st) == 0))
-        return kit_state_busy(k, scope);
+        return kit_state_busy(k);
     if (target == s_idle ||
         (PyUnicode_Check(target) &&
          PyUnicode_Compare(target, s_idle) == 0))
-        return kit_state_idle(k, scope);
+        return kit_state_idle(k);
     return 0;
 }
+
+/* -- the hooks: what the kit's four listeners did, called by the ------ */
+/* -- emissions themselves -------------------------------------------- */
+
+static inline int
+str_is(PyObject *a, PyObject *b)
+{
+    return a == b || (a != NULL && PyUnicode_Check(a) &&
+                      PyUnicode_Compare(a, b) == 0);
+}
+
+/* stateChanged of the socket manager, after the listeners in its list
+ * (where the per-entry registration, always the newest, used to sit) */
+unsigned long
+slotkit_slot_serial(PyObject *kit_)
+{
+    SlotKit *k = (SlotKit *)kit_;
+    if (Py_TYPE(kit_) != &SlotKitType || k->k_slot == NULL)
+        return 0;
+    return k->k_slot->f_hist_n;
+}
+
+int
+slotkit_smgr_hook(PyObject *kit_, PyObject *st, unsigned long serial)
+{
+#if CUEBALL_SLOT_HOOKS
+    SlotKit *k = (SlotKit *)kit_;
+    if (Py_TYPE(kit_) != &SlotKitType || k->k_slot == NULL)
+        return 0;
+    unsigned long now = k->k_slot->f_hist_n;
+    if (now == 0 || now != serial)
+        return 0;       /* the slot moved while the listeners ran */
+    if (now == k->k_busy_serial) {
+        /* record the smgr state as observed through events
+         * (lib/connection-fsm.js:885-890) */
+        Py_INCREF(st);
+        Py_XSETREF(k->k_observed, st);
+        return 0;
+    }
+    if (now == k->k_idle_serial) {
+        Py_INCREF(kit_);
+        int r = kit_idle_smgr_changed(k, st);
+        Py_DECREF(kit_);
+        return r;
+    }
+#else
+    (void)kit_; (void)st;
+#endif
+    return 0;
+}
+
+/* released/closed of a handle whose slot is in the busy state that armed
+ * it: the slot moves on.  Anything else: nothing. */
+static int
+ch_slot_hook(CHOb *h, PyObject *st)
+{
+    PyObject *slot = h->chb_slot;
+    if (h->chb_bk_serial == 0 || slot == NULL ||
+        !PyObject_TypeCheck(slot, &SlotBaseType))
+        return 0;
+    PyObject *kit_ = ((FSMOb *)slot)->f_fastkit;
+    if (kit_ == NULL || Py_TYPE(kit_) != &SlotKitType)
+        return 0;
+    SlotKit *k = (SlotKit *)kit_;
+    if (k->k_slot != (FSMOb *)slot ||
+        k->k_busy_serial != h->chb_bk_serial ||
+        k->k_slot->f_hist_n != h->chb_bk_serial)
+        return 0;       /* the slot has left that busy state: stale */
+    int r = 0;
+    Py_INCREF(kit_);
+    if (str_is(st, s_released))
+        r = kit_busy_on_release(k);
+    else if (str_is(st, s_closed))
+        r = kit_busy_on_close(k);
+    Py_DECREF(kit_);
+    return r;
+}
+
+/* One stateChanged of a claim handle.  Order: the ticket (it used to be
+ * the first listener), the listeners registered before the slot went
+ * busy, the slot, the listeners registered after. */
+int
+ch_emit_state_changed(FSMOb *self, PyObject *st)
+{
+    CHOb *h = (CHOb *)self;
+    /* the listeners of this emission are those there are now: one added
+     * while the ticket or the slot runs (in the claim callback, say)
+     * first hears of the next state */
+    PyObject *ls = NULL;
+    if (self->base.ev_events != NULL) {
+        ls = PyDict_GetItemWithError(self->base.ev_events, s_stateChanged);
+        if (ls == NULL && PyErr_Occurred())
+            return -1;
+    }
+    Py_ssize_t n = ls != NULL ? PyList_GET_SIZE(ls) : 0;
+    int hook = h->chb_bk_serial != 0 &&
+        (str_is(st, s_released) || str_is(st, s_closed));
+    Py_ssize_t pos = !hook ? -1 : h->chb_bk_pos < n ? h->chb_bk_pos : n;
+    PyObject *snap = NULL;
+    if (n > 0) {
+        snap = PyList_GetSlice(ls, 0, n);
+        if (snap == NULL)
+            return -1;
+    }
+    if (h->chb_tk_on && str_is(st, s_waiting)) {
+        if (ch_ticket_try_next(h) < 0) {
+            Py_XDECREF(snap);
+            return -1;
+        }
+    }
+    if (n == 0)
+        return hook ? ch_slot_hook(h, st) : 0;
+    for (Py_ssize_t i = 0; i <= n; i++) {
+        if (i == pos && ch_slot_hook(h, st) < 0) {
+            Py_DECREF(snap);
+            return -1;
+        }
+        if (i == n)
+            break;
+        PyObject *r = PyObject_Vectorcall(PyList_GET_ITEM(snap, i), &st, 1,
+                                          NULL);
+        if (r == NULL) {
+            Py_DECREF(snap);
+            return -1;
+        }
+        Py_DECREF(r);
+    }
+    Py_DECREF(snap);
+    return 1;
+}
+
+/* slot.emit(): `unwanted` reaches the kit after the listeners in the
+ * list, while the slot is in the idle state the kit entered */
+static PyObject *
+Slot_emit(PyObject *self_, PyObject *const *args, Py_ssize_t nargs)
+{
+    if (nargs < 1) {
+        PyErr_SetString(PyExc_TypeError, "emit(event, *args)");
+        return NULL;
+    }
+    FSMOb *slot = (FSMOb *)self_;
+    unsigned long serial = slot->f_hist_n;
+    int r = emitter_emit_core((Emitter *)self_, args[0], args + 1,
+                              nargs - 1);
+    if (r < 0)
+        return NULL;
+#if CUEBALL_SLOT_HOOKS
+    PyObject *kit_ = slot->f_fastkit;
+    if (kit_ != NULL && Py_TYPE(kit_) == &SlotKitType &&
+        str_is(args[0], s_unwanted_evt)) {
+        SlotKit *k = (SlotKit *)kit_;
+        if (k->k_slot == slot && serial != 0 &&
+            slot->f_hist_n == serial && serial == k->k_idle_serial) {
+            Py_INCREF(kit_);
+            int hr = kit_idle_unwanted(k);
+            Py_DECREF(kit_);
+            if (hr < 0)
+                return NULL;
+            r = 1;
+        }
+    }
+#endif
+    return PyBool_FromLong(r);
+}
+
+/* an idle slot listens for `unwanted`, registration or not */
+static PyObject *
+Slot_event_names(PyObject *self_, PyObject *noargs)
+{
+    PyObject *names = Emitter_event_names(self_, noargs);
+#if CUEBALL_SLOT_HOOKS
+    if (names == NULL)
+        return NULL;
+    FSMOb *slot = (FSMOb *)self_;
+    PyObject *kit_ = slot->f_fastkit;
+    if (kit_ != NULL && Py_TYPE(kit_) == &SlotKitType &&
+        ((SlotKit *)kit_)->k_slot == slot && slot->f_hist_n != 0 &&
+        slot->f_hist_n == ((SlotKit *)kit_)->k_idle_serial) {
+        int has = PySequence_Contains(names, s_unwanted_evt);
+        if (has < 0 || (!has && PyList_Append(names, s_unwanted_evt) < 0)) {
+            Py_DECREF(names);
+            return NULL;
+        }
+    }
+#endif
+    return names;
+}
+
+static PyMethodDef Slot_methods[] = {
+    {"emit", (PyCFunction)(void (*)(void))Slot_emit, METH_FASTCALL, NULL},
+    {"event_names", Slot_event_names, METH_NOARGS, NULL},
+    {NULL, NULL, 0, NULL},
+};
 
 /* ------------------------------------------------------------------ */
 /* ControlledDelay: the CoDel AQM (codel.py / lib/codel.js) in C so    */
@@ -5234,6 +5693,7 @@ typedef struct {
     PyObject *sd_codel;     /* owned native ControlledDelay or NULL */
     int sd_has_codel;       /* codel configured but not native =>
                              * python path */
+    vectorcallfunc sd_vectorcall;
 } SlotDispatch;
 
 extern PyTypeObject SlotDispatchType;
@@ -5251,15 +5711,9 @@ sd_fallback(SlotDispatch *d, PyObject *st)
 }
 
 static PyObject *
-SlotDispatch_call(PyObject *self_, PyObject *args, PyObject *kwds)
+slotdispatch_run(PyObject *self_, PyObject *st)
 {
     SlotDispatch *d = (SlotDispatch *)self_;
-    (void)kwds;
-    if (PyTuple_GET_SIZE(args) != 1) {
-        PyErr_SetString(PyExc_TypeError, "SlotDispatch(state)");
-        return NULL;
-    }
-    PyObject *st = PyTuple_GET_ITEM(args, 0);
     FSMOb *fsm = (FSMOb *)d->sd_fsm;
 
     /* common preconditions for both fast paths */
@@ -5411,6 +5865,29 @@ SlotDispatch_call(PyObject *self_, PyObject *args, PyObject *kwds)
     Py_RETURN_NONE;
 }
 
+static PyObject *
+SlotDispatch_call(PyObject *self_, PyObject *args, PyObject *kwds)
+{
+    (void)kwds;
+    if (PyTuple_GET_SIZE(args) != 1) {
+        PyErr_SetString(PyExc_TypeError, "SlotDispatch(state)");
+        return NULL;
+    }
+    return slotdispatch_run(self_, PyTuple_GET_ITEM(args, 0));
+}
+
+static PyObject *
+SlotDispatch_vectorcall(PyObject *self_, PyObject *const *args,
+                        size_t nargsf, PyObject *kwnames)
+{
+    if (PyVectorcall_NARGS(nargsf) != 1 ||
+        (kwnames != NULL && PyTuple_GET_SIZE(kwnames) != 0)) {
+        PyErr_SetString(PyExc_TypeError, "SlotDispatch(state)");
+        return NULL;
+    }
+    return slotdispatch_run(self_, args[0]);
+}
+
 static int
 SlotDispatch_traverse(PyObject *self_, visitproc visit, void *arg)
 {
@@ -5485,6 +5962,7 @@ SlotDispatch_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
     d->sd_waiters = (NQueue *)wq;
     d->sd_has_codel = PyObject_IsTrue(has_codel);
     d->sd_codel = NULL;
+    d->sd_vectorcall = SlotDispatch_vectorcall;
     PyObject_GC_Track((PyObject *)d);
     if (d->sd_has_codel) {
         PyObject *cd = PyObject_GetAttrString(pool, "p_codel");
@@ -5514,8 +5992,6 @@ SlotKit_traverse(PyObject *self_, visitproc visit, void *arg)
     Py_VISIT((PyObject *)k->k_slot);
     Py_VISIT(k->k_smgr);
     Py_VISIT(k->k_observed);
-    Py_VISIT((PyObject *)k->k_busy_scope);
-    Py_VISIT((PyObject *)k->k_idle_scope);
     for (int i = 0; i < KCB_N; i++)
         Py_VISIT(k->k_cbs[i]);
     return 0;
@@ -5528,8 +6004,6 @@ SlotKit_clear_(PyObject *self_)
     Py_CLEAR(k->k_slot);
     Py_CLEAR(k->k_smgr);
     Py_CLEAR(k->k_observed);
-    Py_CLEAR(k->k_busy_scope);
-    Py_CLEAR(k->k_idle_scope);
     for (int i = 0; i < KCB_N; i++)
         Py_CLEAR(k->k_cbs[i]);
     return 0;
@@ -5565,8 +6039,8 @@ SlotKit_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
     Py_INCREF(smgr);
     k->k_smgr = smgr;
     k->k_observed = NULL;
-    k->k_busy_scope = NULL;
-    k->k_idle_scope = NULL;
+    k->k_busy_serial = 0;
+    k->k_idle_serial = 0;
     for (int i = 0; i < KCB_N; i++)
         k->k_cbs[i] = NULL;
     PyObject_GC_Track((PyObject *)k);
@@ -5579,9 +6053,15 @@ SlotKit_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
         Py_INCREF((PyObject *)k);
         cb->kc_kit = k;
         cb->kc_which = i;
+        cb->kc_vectorcall = KitCb_vectorcall;
         PyObject_GC_Track((PyObject *)cb);
         k->k_cbs[i] = (PyObject *)cb;
     }
+#if CUEBALL_SLOT_HOOKS
+    /* the socket manager's emissions call this kit (slotkit_smgr_hook) */
+    Py_INCREF((PyObject *)k);
+    Py_XSETREF(((FSMOb *)smgr)->f_watchkit, (PyObject *)k);
+#endif
     return (PyObject *)k;
 }
 
@@ -5615,6 +6095,188 @@ slotkit_types_init(void)
     SlotDispatchType.tp_traverse = SlotDispatch_traverse;
     SlotDispatchType.tp_clear = SlotDispatch_clear_;
     SlotDispatchType.tp_new = SlotDispatch_new;
+
+    SlotBaseType.tp_methods = Slot_methods;
+#if CUEBALL_VECTORCALL
+    /* emission and the event loop call these without building a tuple */
+    KitCbType.tp_vectorcall_offset = offsetof(KitCb, kc_vectorcall);
+    KitCbType.tp_flags |= Py_TPFLAGS_HAVE_VECTORCALL;
+    SlotDispatchType.tp_vectorcall_offset =
+        offsetof(SlotDispatch, sd_vectorcall);
+    SlotDispatchType.tp_flags |= Py_TPFLAGS_HAVE_VECTORCALL;
+    FlushBatchType.tp_vectorcall_offset = offsetof(FlushBatch, fb_vectorcall);
+    FlushBatchType.tp_flags |= Py_TPFLAGS_HAVE_VECTORCALL;
+#endif
+}
+
+/* ------------------------------------------------------------------ */
+/* ClaimMethod: ConnectionPool.claim as a method descriptor.  The      */
+/* positional claim({}, cb) / claim(None, cb) on a running pool        */
+/* without CoDel goes straight to pool_claim, with no Python frame;    */
+/* every other shape (keywords, options, claim(cb), CoDel, a pool that */
+/* is not running) calls the Python function it wraps, unchanged.      */
+
+PyObject *s_p_codel;             /* "p_codel" */
+PyObject *s_p_claim_log;         /* "p_claim_log" */
+
+typedef struct {
+    PyObject_HEAD
+    PyObject *cm_func;           /* the Python ConnectionPool.claim */
+    PyObject *cm_handle_cls;     /* ClaimHandle */
+    PyObject *cm_doc;
+    PyObject *cm_name;
+    PyObject *cm_qualname;
+    PyObject *cm_module;
+    vectorcallfunc cm_vectorcall;
+} ClaimMethod;
+
+extern PyTypeObject ClaimMethodType;
+
+static PyObject *
+ClaimMethod_vectorcall(PyObject *self_, PyObject *const *args,
+                       size_t nargsf, PyObject *kwnames)
+{
+    ClaimMethod *cm = (ClaimMethod *)self_;
+    if (PyVectorcall_NARGS(nargsf) == 3 &&
+        (kwnames == NULL || PyTuple_GET_SIZE(kwnames) == 0)) {
+        PyObject *pool = args[0], *opt = args[1], *cb = args[2];
+        if (cb != Py_None &&
+            (opt == Py_None ||
+             (PyDict_CheckExact(opt) && PyDict_GET_SIZE(opt) == 0)) &&
+            PyObject_TypeCheck(pool, &FSMType)) {
+            PyObject *pst = ((FSMOb *)pool)->f_state;
+            int open = pst != NULL &&
+                (pst == s_running_st ||
+                 PyUnicode_Compare(pst, s_running_st) == 0 ||
+                 PyUnicode_CompareWithASCIIString(pst, "starting") == 0);
+            PyObject *codel = open ? PyObject_GetAttr(pool, s_p_codel)
+                                   : NULL;
+            if (open && codel == NULL)
+                return NULL;
+            Py_XDECREF(codel);
+            if (open && codel == Py_None) {
+                PyObject *log = PyObject_GetAttr(pool, s_p_claim_log);
+                if (log == NULL)
+                    return NULL;
+                PyObject *pargs[5] = {cm->cm_handle_cls, pool, cb, log,
+                                      ((FSMOb *)pool)->f_loop};
+                PyObject *h = speed_pool_claim(NULL, pargs, 5);
+                Py_DECREF(log);
+                return h;
+            }
+        }
+    }
+    return PyObject_Vectorcall(cm->cm_func, args, nargsf, kwnames);
+}
+
+static PyObject *
+ClaimMethod_descr_get(PyObject *self_, PyObject *obj, PyObject *type)
+{
+    (void)type;
+    if (obj == NULL || obj == Py_None) {
+        Py_INCREF(self_);
+        return self_;
+    }
+    return PyMethod_New(self_, obj);
+}
+
+static int
+ClaimMethod_traverse(PyObject *self_, visitproc visit, void *arg)
+{
+    ClaimMethod *cm = (ClaimMethod *)self_;
+    Py_VISIT(cm->cm_func);
+    Py_VISIT(cm->cm_handle_cls);
+    return 0;
+}
+
+static int
+ClaimMethod_clear_(PyObject *self_)
+{
+    ClaimMethod *cm = (ClaimMethod *)self_;
+    Py_CLEAR(cm->cm_func);
+    Py_CLEAR(cm->cm_handle_cls);
+    Py_CLEAR(cm->cm_doc);
+    Py_CLEAR(cm->cm_name);
+    Py_CLEAR(cm->cm_qualname);
+    Py_CLEAR(cm->cm_module);
+    return 0;
+}
+
+static void
+ClaimMethod_dealloc(PyObject *self_)
+{
+    PyObject_GC_UnTrack(self_);
+    ClaimMethod_clear_(self_);
+    PyObject_GC_Del(self_);
+}
+
+static PyMemberDef ClaimMethod_members[] = {
+    {(char *)"__wrapped__", T_OBJECT, offsetof(ClaimMethod, cm_func),
+     READONLY, NULL},
+    {(char *)"__doc__", T_OBJECT, offsetof(ClaimMethod, cm_doc), READONLY,
+     NULL},
+    {(char *)"__name__", T_OBJECT, offsetof(ClaimMethod, cm_name), READONLY,
+     NULL},
+    {(char *)"__qualname__", T_OBJECT, offsetof(ClaimMethod, cm_qualname),
+     READONLY, NULL},
+    {(char *)"__module__", T_OBJECT, offsetof(ClaimMethod, cm_module),
+     READONLY, NULL},
+    {NULL, 0, 0, 0, NULL},
+};
+
+PyTypeObject ClaimMethodType = {
+    PyVarObject_HEAD_INIT(NULL, 0)
+    "cueball_amd._speed._ClaimMethod",
+    sizeof(ClaimMethod),
+};
+
+static void
+claim_method_type_init(void)
+{
+    ClaimMethodType.tp_dealloc = ClaimMethod_dealloc;
+    ClaimMethodType.tp_vectorcall_offset =
+        offsetof(ClaimMethod, cm_vectorcall);
+    ClaimMethodType.tp_call = PyVectorcall_Call;
+    ClaimMethodType.tp_flags = Py_TPFLAGS_DEFAULT | Py_TPFLAGS_HAVE_GC |
+        Py_TPFLAGS_HAVE_VECTORCALL | Py_TPFLAGS_METHOD_DESCRIPTOR;
+    ClaimMethodType.tp_traverse = ClaimMethod_traverse;
+    ClaimMethodType.tp_clear = ClaimMethod_clear_;
+    ClaimMethodType.tp_members = ClaimMethod_members;
+    ClaimMethodType.tp_descr_get = ClaimMethod_descr_get;
+}
+
+/* claim_method(func, handle_cls) -> the descriptor to put on the pool
+ * class in place of func (func itself in a build without the entry) */
+static PyObject *
+speed_claim_method(PyObject *mod, PyObject *const *args, Py_ssize_t nargs)
+{
+    (void)mod;
+    if (nargs != 2 || !PyCallable_Check(args[0]) || !PyType_Check(args[1]) ||
+        !PyType_IsSubtype((PyTypeObject *)args[1], &CHType)) {
+        PyErr_SetString(PyExc_TypeError,
+                        "claim_method(func, ClaimHandleBase subclass)");
+        return NULL;
+    }
+#if !CUEBALL_VECTORCALL
+    Py_INCREF(args[0]);
+    return args[0];
+#else
+    ClaimMethod *cm = PyObject_GC_New(ClaimMethod, &ClaimMethodType);
+    if (cm == NULL)
+        return NULL;
+    Py_INCREF(args[0]);
+    cm->cm_func = args[0];
+    Py_INCREF(args[1]);
+    cm->cm_handle_cls = args[1];
+    cm->cm_vectorcall = ClaimMethod_vectorcall;
+    cm->cm_doc = PyObject_GetAttrString(args[0], "__doc__");
+    cm->cm_name = PyObject_GetAttrString(args[0], "__name__");
+    cm->cm_qualname = PyObject_GetAttrString(args[0], "__qualname__");
+    cm->cm_module = PyObject_GetAttrString(args[0], "__module__");
+    PyErr_Clear();               /* a callable without one: reads None */
+    PyObject_GC_Track((PyObject *)cm);
+    return (PyObject *)cm;
+#endif
 }
 
 PyObject *
@@ -5646,6 +6308,8 @@ PyMethodDef speed_methods[] = {
     {"claim_fast", (PyCFunction)(void (*)(void))speed_claim_fast,
      METH_FASTCALL, NULL},
     {"pool_claim", (PyCFunction)(void (*)(void))speed_pool_claim,
+     METH_FASTCALL, NULL},
+    {"claim_method", (PyCFunction)(void (*)(void))speed_claim_method,
      METH_FASTCALL, NULL},
     {NULL, NULL, 0, NULL},
 };
@@ -5746,6 +6410,9 @@ PyInit__speed(void)
     ct_type_init();
     slotkit_types_init();
     codel_type_init();
+    claim_method_type_init();
+    s_p_codel = PyUnicode_InternFromString("p_codel");
+    s_p_claim_log = PyUnicode_InternFromString("p_claim_log");
     s_p_lat = PyUnicode_InternFromString("p_lat");
     latency_types_init();
     if (PyType_Ready(&LatHistType) < 0 ||
@@ -5768,6 +6435,7 @@ PyInit__speed(void)
         PyType_Ready(&KitCbType) < 0 ||
         PyType_Ready(&SlotKitType) < 0 ||
         PyType_Ready(&SlotDispatchType) < 0 ||
+        PyType_Ready(&ClaimMethodType) < 0 ||
         PyType_Ready(&CoDelType) < 0)
         return NULL;
 
@@ -5776,6 +6444,11 @@ PyInit__speed(void)
     if (g_remove_desc == NULL)
         return NULL;
     Py_INCREF(g_remove_desc);
+    g_ch_remove_desc = PyDict_GetItemString(CHType.tp_dict,
+                                            "remove_listener");
+    if (g_ch_remove_desc == NULL)
+        return NULL;
+    Py_INCREF(g_ch_remove_desc);
     if (ch_entries_init() < 0)
         return NULL;
     g_inf = PyFloat_FromDouble(HUGE_VAL);

@@ -87,10 +87,11 @@ class _ClaimTicket:
     to 'waiting' (registered as the handle's stateChanged listener; the
     closure-free form of lib/pool.js:922-968, on the claim hot path).
 
-    When the native core is loaded, ``_speed.ClaimTicket`` replaces
-    this class on the claim path: it performs the idle-queue handoff
-    entirely in C and delegates everything else to the same
-    ``pool._ticket_slow`` this class uses."""
+    When the native core is loaded, its own ticket replaces this class
+    on the claim path: a hook of the native handle, not a registered
+    listener, that performs the idle-queue handoff entirely in C and
+    delegates everything else to the same ``pool._ticket_slow`` this
+    class uses (``_speed.ClaimTicket`` is that code as a listener)."""
 
     __slots__ = ("pool", "handle", "err_on_empty")
 
@@ -1812,3 +1813,12 @@ class ConnectionPool(FSM):
         except asyncio.CancelledError:
             res.cancel()
             raise
+
+
+if _native_pool_claim is not None:
+    # claim({}, cb) on a running pool without CoDel enters the native core
+    # without a Python frame; every other call shape runs the function
+    # above (cueball_amd/_native/speed.cpp, ClaimMethod)
+    from ._speed import claim_method as _claim_method
+    ConnectionPool.claim = _claim_method(  # type: ignore[assignment]
+        ConnectionPool.__dict__["claim"], ClaimHandle)
