@@ -50,6 +50,12 @@
 #ifndef CUEBALL_VECTORCALL
 #define CUEBALL_VECTORCALL 1
 #endif
+#ifndef CUEBALL_EXACT_TYPES
+#define CUEBALL_EXACT_TYPES 1
+#endif
+#ifndef CUEBALL_VALID_IDENTITY
+#define CUEBALL_VALID_IDENTITY 1
+#endif
 #if !defined(Py_TPFLAGS_HAVE_VECTORCALL) && defined(_Py_TPFLAGS_HAVE_VECTORCALL)
 #define Py_TPFLAGS_HAVE_VECTORCALL _Py_TPFLAGS_HAVE_VECTORCALL
 #endif
@@ -1091,6 +1097,8 @@ struct FSMOb {
     PyObject *f_watchkit;       /* SlotKit* or NULL, on a socket manager:
                                  * the kit whose slot reacts to this
                                  * FSM's stateChanged while busy or idle */
+    PyObject *f_ctx;            /* PoolCtx* or NULL, on a pool: what the
+                                 * claim cycle reads of it (pool_ctx) */
     int f_entering;
     int f_emit_scheduled;
 };
@@ -1131,6 +1139,47 @@ typedef PyObject *(*ch_entry_fn)(PyObject *, PyObject *);
 ch_entry_fn ch_direct_entry(FSMOb *self, PyObject *target);
 
 extern PyTypeObject FSMType;
+extern PyTypeObject SlotBaseType;
+
+/* The objects of the claim cycle are instances of three Python classes
+ * (ClaimHandle, ConnectionSlotFSM, ConnectionPool), never of the native
+ * bases themselves, so PyObject_TypeCheck's exact-type shortcut misses
+ * and every test walks the MRO.  The classes are registered at import
+ * (owned references); a type that is none of them gets the walk. */
+PyTypeObject *g_handle_cls;    /* connection_fsm.ClaimHandle */
+PyTypeObject *g_slot_cls;      /* connection_fsm.ConnectionSlotFSM */
+PyTypeObject *g_pool_cls;      /* pool.ConnectionPool */
+
+static inline int
+is_handle(PyObject *x)
+{
+#if CUEBALL_EXACT_TYPES
+    if (Py_TYPE(x) == g_handle_cls)
+        return 1;
+#endif
+    return PyObject_TypeCheck(x, &CHType);
+}
+
+static inline int
+is_slot(PyObject *x)
+{
+#if CUEBALL_EXACT_TYPES
+    if (Py_TYPE(x) == g_slot_cls)
+        return 1;
+#endif
+    return PyObject_TypeCheck(x, &SlotBaseType);
+}
+
+static inline int
+is_fsm(PyObject *x)
+{
+#if CUEBALL_EXACT_TYPES
+    PyTypeObject *tp = Py_TYPE(x);
+    if (tp == g_pool_cls || tp == g_slot_cls || tp == g_handle_cls)
+        return 1;
+#endif
+    return PyObject_TypeCheck(x, &FSMType);
+}
 
 PyObject *
 fsm_get_loop_of(FSMOb *fsm)
@@ -1216,7 +1265,7 @@ fsm_flush_core(FSMOb *self)
 {
     self->f_emit_scheduled = 0;
     int n = 0;
-    int is_handle = PyObject_TypeCheck((PyObject *)self, &CHType);
+    int handle = is_handle((PyObject *)self);
     while (self->f_eq_head < self->f_eq_len && n++ < FSM_FLUSH_CAP) {
         /* pop by index; listeners may queue more (or flush again)
          * while they run, so the queue is read afresh every turn */
@@ -1224,7 +1273,7 @@ fsm_flush_core(FSMOb *self)
         if (self->f_eq_head == self->f_eq_len)
             self->f_eq_head = self->f_eq_len = 0;
         int r;
-        if (is_handle) {
+        if (handle) {
             r = ch_emit_state_changed(self, st);
         } else {
             PyObject *eargs[2] = {s_stateChanged, st};
@@ -1477,6 +1526,18 @@ check_valid(FSMOb *self, PyObject *from, PyObject *state)
 {
     if (self->f_valid == NULL)
         return 0;
+#if CUEBALL_VALID_IDENTITY
+    /* the native cycle's f_valid is one of this module's constant tuples
+     * and `state` one of its interned names: found by identity, no rich
+     * compare.  Anything else (a list, an equal string that is another
+     * object, a miss) is answered by the sequence protocol as before. */
+    if (PyTuple_CheckExact(self->f_valid)) {
+        PyObject *v = self->f_valid;
+        for (Py_ssize_t i = 0, n = PyTuple_GET_SIZE(v); i < n; i++)
+            if (PyTuple_GET_ITEM(v, i) == state)
+                return 0;
+    }
+#endif
     int c = PySequence_Contains(self->f_valid, state);
     if (c < 0)
         return -1;
@@ -1614,7 +1675,7 @@ fsm_enter_loop(FSMOb *self, PyObject *state)
      * counting.  Without this every claim leaves cyclic garbage and
      * CPython's cyclic GC pauses dominate claim p99 (measured 4x). */
     if (self->f_valid == t_empty &&
-        PyObject_TypeCheck((PyObject *)self, &CHType))
+        is_handle((PyObject *)self))
         ch_terminal_cleanup(self);
     return 0;
 }
@@ -1945,6 +2006,7 @@ FSM_traverse(PyObject *self_, visitproc visit, void *arg)
     Py_VISIT(self->f_flush_bound);
     Py_VISIT(self->f_fastkit);
     Py_VISIT(self->f_watchkit);
+    Py_VISIT(self->f_ctx);
     return Emitter_traverse(self_, visit, arg);
 }
 
@@ -1964,6 +2026,7 @@ FSM_clear_(PyObject *self_)
     Py_CLEAR(self->f_flush_bound);
     Py_CLEAR(self->f_fastkit);
     Py_CLEAR(self->f_watchkit);
+    Py_CLEAR(self->f_ctx);
     return Emitter_clear_(self_);
 }
 
@@ -2007,10 +2070,23 @@ PyMemberDef FSM_members[] = {
     {NULL, 0, 0, 0, NULL},
 };
 
+/* a pool's claim context, None until its first native claim or dispatch */
+PyObject *
+FSM_get__claim_ctx(PyObject *self_, void *closure)
+{
+    PyObject *cx = ((FSMOb *)self_)->f_ctx;
+    (void)closure;
+    if (cx == NULL)
+        Py_RETURN_NONE;
+    Py_INCREF(cx);
+    return cx;
+}
+
 PyGetSetDef FSM_getset[] = {
     {(char *)"_fsm_state", FSM_get__fsm_state, NULL, NULL, NULL},
     {(char *)"_fsm_valid", FSM_get__fsm_valid, FSM_set__fsm_valid, NULL,
      NULL},
+    {(char *)"_claim_ctx", FSM_get__claim_ctx, NULL, NULL, NULL},
     {NULL, NULL, NULL, NULL, NULL},
 };
 
@@ -2573,36 +2649,65 @@ extern PyObject *s_busy_st;
  * on `slot` (borrowed), or NULL if the slot has no kit */
 PyObject *slotkit_conn_err_cb(PyObject *slot, PyObject *handle);
 
+/* What the claim cycle reads of its pool on every claim and never sees
+ * change: ConnectionPool.__init__ binds these attributes once and only
+ * mutates the objects afterwards (docs/internals.md).  One context hangs
+ * off the pool's FSMOb (f_ctx, made by pool_ctx() on the first native
+ * claim or dispatch) and every handle of the pool refers to it.  It does
+ * not refer to the pool.  A handle whose pool has none (not a native FSM,
+ * or without these attributes), or whose log is not the pool's claim log,
+ * owns a private one that holds its latency recorder and log. */
+struct NQueue;
+typedef struct {
+    PyObject_HEAD
+    struct NQueue *pc_idleq;     /* the three queues if all are the native */
+    struct NQueue *pc_waiters;   /* deque, else all NULL */
+    struct NQueue *pc_initq;
+    PyObject *pc_counters;       /* p_counters (a dict); NULL if private */
+    PyObject *pc_dead;           /* p_dead (a dict); NULL if private */
+    PoolLatOb *pc_lat;           /* p_lat if it is a PoolLatency, or NULL */
+    PyObject *pc_log;            /* p_claim_log, or the handle's own log */
+    int pc_no_codel;             /* p_codel is None */
+} PoolCtx;
+
+extern PyTypeObject PoolCtxType;
+/* the pool's context, made if need be; NULL (no error set) if `pool` is
+ * not a native FSM with the attributes of a ConnectionPool.  Borrowed. */
+PoolCtx *pool_ctx(PyObject *pool);
+/* a handle's own context: `lat` and `log`, the queues of `base` if any */
+PoolCtx *pool_ctx_private(PoolCtx *base, PoolLatOb *lat, PyObject *log);
+
 typedef struct {
     FSMOb base;
     PyObject *chb_pool;
     PyObject *chb_claim_stack;
     PyObject *chb_callback;
-    PyObject *chb_log;
     PyObject *chb_slot;
     PyObject *chb_release_stack;
     PyObject *chb_connection;
     PyObject *chb_last_error;
     PyObject *chb_waiter_node; /* ch_waiter_node: NULL or None unless
                                 * the handle sits in the waiter queue */
-    PoolLatOb *chb_lat;     /* the pool's latency recorder, or NULL */
+    PoolCtx *chb_ctx;       /* owned: the pool's context or a private one
+                             * (latency recorder, log, queues); NULL
+                             * before _setup */
     double chb_claim_timeout;
     double chb_started;
     double chb_claimed_at;  /* valid while chb_lat_open */
-    long chb_pre[4];
-    int chb_have_pre;
-    int chb_throw_error;
-    int chb_cancelled;
-    int chb_leak_check;
-    int chb_pinger;
-    int chb_lat_open;       /* wait recorded, hold still running */
+    int chb_pre[4];         /* the leak detector's "before" counts */
+    /* flags, one byte each (four are members, see CH_members) */
+    unsigned char chb_have_pre;
+    unsigned char chb_throw_error;
+    unsigned char chb_cancelled;
+    unsigned char chb_leak_check;
+    unsigned char chb_pinger;
+    unsigned char chb_lat_open;  /* wait recorded, hold still running */
     /* The library's own two listeners of a handle are not list entries.
      * The ticket: while chb_tk_on, every return to "waiting" runs the
-     * pool's idle-queue handoff before any listener is called; the
-     * three queues are the pool's (Queue objects, owned). */
-    PyObject *chb_idleq, *chb_waiters, *chb_initq;
-    int chb_tk_on;
-    int chb_tk_err_on_empty;
+     * pool's idle-queue handoff before any listener is called, on the
+     * three queues of chb_ctx. */
+    unsigned char chb_tk_on;
+    unsigned char chb_tk_err_on_empty;
     /* The busy slot: armed by the slot kit's busy entry with the slot's
      * transition count at that entry (0 = not armed) and the number of
      * stateChanged listeners the handle had then.  On released/closed
@@ -2613,6 +2718,20 @@ typedef struct {
 } CHOb;
 
 extern PyTypeObject CHType;
+
+static inline PoolLatOb *
+ch_lat(CHOb *h)
+{
+    return h->chb_ctx != NULL ? h->chb_ctx->pc_lat : NULL;
+}
+
+/* the handle's log (borrowed); None before _setup */
+static inline PyObject *
+ch_log(CHOb *h)
+{
+    return h->chb_ctx != NULL && h->chb_ctx->pc_log != NULL
+        ? h->chb_ctx->pc_log : Py_None;
+}
 
 long
 c_count_listeners(PyObject *emitter, PyObject *event)
@@ -2767,7 +2886,7 @@ conn_err_fire(CHOb *h, PyObject *err)
         "connection emitted error while claimed");
     if (msg == NULL)
         return NULL;
-    PyObject *r = PyObject_CallMethodObjArgs(h->chb_log, s_warn, msg,
+    PyObject *r = PyObject_CallMethodObjArgs(ch_log(h), s_warn, msg,
                                              NULL);
     Py_DECREF(msg);
     if (r == NULL)
@@ -3135,7 +3254,7 @@ CH_state_claiming(PyObject *self_, PyObject *scope)
     PyObject *slot = self->chb_slot;
     /* inline of ConnectionSlotFSM.claim() when the slot runs the
      * native busy/idle cycle (same checks, same transition) */
-    if (slot != NULL && PyObject_TypeCheck(slot, &SlotBaseType) &&
+    if (slot != NULL && is_slot(slot) &&
         ((FSMOb *)slot)->f_fastkit != NULL) {
         FSMOb *sf = (FSMOb *)slot;
         PyObject *fs = sf->f_state;
@@ -3175,12 +3294,13 @@ CH_state_claimed(PyObject *self_, PyObject *scope)
     }
 
     PyObject *conn = self->chb_connection;
-    int lk = emitter_leak_counts(conn, self->chb_pre);
+    long pre[4] = {0, 0, 0, 0};
+    int lk = emitter_leak_counts(conn, pre);
     if (lk == -1)
         return NULL;
-    if (lk == -2)
-        self->chb_pre[0] = self->chb_pre[1] = self->chb_pre[2] =
-            self->chb_pre[3] = 0;
+    /* listener counts: they fit an int (-2, not an emitter: zeros) */
+    for (int i = 0; i < 4; i++)
+        self->chb_pre[i] = lk == -2 ? 0 : (int)pre[i];
     self->chb_have_pre = 1;
 
     /* the slot's kit keeps one error callback for all its claims; a
@@ -3212,12 +3332,13 @@ CH_state_claimed(PyObject *self_, PyObject *scope)
 
     /* the wait ends here, just before the user callback; pinger
      * claims are the pool's own and not counted */
-    if (self->chb_lat != NULL && !self->chb_pinger) {
+    PoolLatOb *lat = ch_lat(self);
+    if (lat != NULL && !self->chb_pinger) {
         int err = 0;
-        double now = poollat_now_ms(self->chb_lat, &err);
+        double now = poollat_now_ms(lat, &err);
         if (err)
             return NULL;
-        self->chb_lat->pl_wait->h.record_ms(now - self->chb_started);
+        lat->pl_wait->h.record_ms(now - self->chb_started);
         self->chb_claimed_at = now;
         self->chb_lat_open = 1;
     }
@@ -3238,11 +3359,14 @@ ch_record_hold(CHOb *self)
     if (!self->chb_lat_open)
         return 0;
     self->chb_lat_open = 0;
+    PoolLatOb *lat = ch_lat(self);
+    if (lat == NULL)
+        return 0;
     int err = 0;
-    double now = poollat_now_ms(self->chb_lat, &err);
+    double now = poollat_now_ms(lat, &err);
     if (err)
         return -1;
-    self->chb_lat->pl_hold->h.record_ms(now - self->chb_claimed_at);
+    lat->pl_hold->h.record_ms(now - self->chb_claimed_at);
     return 0;
 }
 
@@ -3268,14 +3392,14 @@ CH_state_released(PyObject *self_, PyObject *scope)
         Py_RETURN_NONE;
     for (int i = 0; i < 4; i++) {
         long c = after[i];
-        if (c > self->chb_pre[i]) {
+        if (c > (long)self->chb_pre[i]) {
             PyObject *msg = PyUnicode_FromFormat(
                 "connection claimer looks like it leaked event handlers "
                 "(event=%S before=%ld after=%ld)",
-                s_leak_events[i], self->chb_pre[i], c);
+                s_leak_events[i], (long)self->chb_pre[i], c);
             if (msg == NULL)
                 return NULL;
-            PyObject *r = PyObject_CallMethodObjArgs(self->chb_log, s_warn,
+            PyObject *r = PyObject_CallMethodObjArgs(ch_log(self), s_warn,
                                                      msg, NULL);
             Py_DECREF(msg);
             if (r == NULL)
@@ -3421,16 +3545,12 @@ CH_traverse(PyObject *self_, visitproc visit, void *arg)
     Py_VISIT(self->chb_pool);
     Py_VISIT(self->chb_claim_stack);
     Py_VISIT(self->chb_callback);
-    Py_VISIT(self->chb_log);
     Py_VISIT(self->chb_slot);
     Py_VISIT(self->chb_release_stack);
     Py_VISIT(self->chb_connection);
     Py_VISIT(self->chb_last_error);
     Py_VISIT(self->chb_waiter_node);
-    Py_VISIT((PyObject *)self->chb_lat);
-    Py_VISIT(self->chb_idleq);
-    Py_VISIT(self->chb_waiters);
-    Py_VISIT(self->chb_initq);
+    Py_VISIT((PyObject *)self->chb_ctx);
     return FSM_traverse(self_, visit, arg);
 }
 
@@ -3441,16 +3561,12 @@ CH_clear_(PyObject *self_)
     Py_CLEAR(self->chb_pool);
     Py_CLEAR(self->chb_claim_stack);
     Py_CLEAR(self->chb_callback);
-    Py_CLEAR(self->chb_log);
     Py_CLEAR(self->chb_slot);
     Py_CLEAR(self->chb_release_stack);
     Py_CLEAR(self->chb_connection);
     Py_CLEAR(self->chb_last_error);
     Py_CLEAR(self->chb_waiter_node);
-    Py_CLEAR(self->chb_lat);
-    Py_CLEAR(self->chb_idleq);
-    Py_CLEAR(self->chb_waiters);
-    Py_CLEAR(self->chb_initq);
+    Py_CLEAR(self->chb_ctx);
     return FSM_clear_(self_);
 }
 
@@ -3480,7 +3596,6 @@ CH__setup(PyObject *self_, PyObject *const *args, Py_ssize_t nargs)
     Py_INCREF(args[0]); Py_XSETREF(self->chb_pool, args[0]);
     Py_INCREF(args[1]); Py_XSETREF(self->chb_claim_stack, args[1]);
     Py_INCREF(args[2]); Py_XSETREF(self->chb_callback, args[2]);
-    Py_INCREF(args[3]); Py_XSETREF(self->chb_log, args[3]);
     self->chb_claim_timeout = PyFloat_AsDouble(args[4]);
     if (self->chb_claim_timeout == -1.0 && PyErr_Occurred())
         return NULL;
@@ -3493,13 +3608,29 @@ CH__setup(PyObject *self_, PyObject *const *args, Py_ssize_t nargs)
     self->chb_pinger = 0;
     self->chb_have_pre = 0;
     self->chb_lat_open = 0;
-    /* the pool's latency recorder, if it keeps one (latencyStats) */
-    PyObject *lat = NULL;
-    if (_PyObject_LookupAttr(args[0], s_p_lat, &lat) < 0)
-        return NULL;
-    if (lat != NULL && Py_TYPE(lat) != &PoolLatType)
-        Py_CLEAR(lat);
-    Py_XSETREF(self->chb_lat, (PoolLatOb *)lat);
+    /* the pool's context holds its latency recorder (if it keeps one,
+     * latencyStats), its queues and its claim log; with another log, or
+     * a pool that has no context, the handle gets one of its own */
+    PoolCtx *cx = pool_ctx(args[0]);
+    if (cx != NULL && cx->pc_log == args[3]) {
+        Py_INCREF((PyObject *)cx);
+    } else {
+        PyObject *lat = NULL;
+        if (cx != NULL) {
+            lat = (PyObject *)cx->pc_lat;
+            Py_XINCREF(lat);
+        } else {
+            if (_PyObject_LookupAttr(args[0], s_p_lat, &lat) < 0)
+                return NULL;
+            if (lat != NULL && Py_TYPE(lat) != &PoolLatType)
+                Py_CLEAR(lat);
+        }
+        cx = pool_ctx_private(cx, (PoolLatOb *)lat, args[3]);
+        Py_XDECREF(lat);
+        if (cx == NULL)
+            return NULL;
+    }
+    Py_XSETREF(self->chb_ctx, cx);
 
     /* FSM init (resolves loop, enters "waiting") */
     PyObject *resolved = resolve_loop(args[6]);
@@ -3515,11 +3646,12 @@ CH__setup(PyObject *self_, PyObject *const *args, Py_ssize_t nargs)
     self->chb_bk_serial = 0;
     if (fsm_goto_state(&self->base, s_waiting) < 0)
         return NULL;
-    if (self->chb_lat != NULL && self->chb_lat->pl_direct &&
-        self->chb_lat->pl_loop == self->base.f_loop) {
+    PoolLatOb *plat = ch_lat(self);
+    if (plat != NULL && plat->pl_direct &&
+        plat->pl_loop == self->base.f_loop) {
         /* stock loop clock: same reading without the python call */
         int err = 0;
-        self->chb_started = poollat_now_ms(self->chb_lat, &err);
+        self->chb_started = poollat_now_ms(plat, &err);
         if (err)
             return NULL;
         Py_RETURN_NONE;
@@ -3572,7 +3704,6 @@ PyMemberDef CH_members[] = {
      0, NULL},
     {(char *)"ch_callback", T_OBJECT, offsetof(CHOb, chb_callback), 0,
      NULL},
-    {(char *)"ch_log", T_OBJECT, offsetof(CHOb, chb_log), 0, NULL},
     {(char *)"ch_slot", T_OBJECT, offsetof(CHOb, chb_slot), 0, NULL},
     {(char *)"ch_release_stack", T_OBJECT,
      offsetof(CHOb, chb_release_stack), 0, NULL},
@@ -3585,17 +3716,28 @@ PyMemberDef CH_members[] = {
     {(char *)"ch_claim_timeout", T_DOUBLE,
      offsetof(CHOb, chb_claim_timeout), 0, NULL},
     {(char *)"ch_started", T_DOUBLE, offsetof(CHOb, chb_started), 0, NULL},
-    {(char *)"ch_cancelled", T_INT, offsetof(CHOb, chb_cancelled), 0,
+    {(char *)"ch_cancelled", T_UBYTE, offsetof(CHOb, chb_cancelled), 0,
      NULL},
-    {(char *)"ch_throw_error", T_INT, offsetof(CHOb, chb_throw_error), 0,
+    {(char *)"ch_throw_error", T_UBYTE, offsetof(CHOb, chb_throw_error), 0,
      NULL},
-    {(char *)"ch_do_release_leak_check", T_INT,
+    {(char *)"ch_do_release_leak_check", T_UBYTE,
      offsetof(CHOb, chb_leak_check), 0, NULL},
-    {(char *)"ch_pinger", T_INT, offsetof(CHOb, chb_pinger), 0, NULL},
+    {(char *)"ch_pinger", T_UBYTE, offsetof(CHOb, chb_pinger), 0, NULL},
     {NULL, 0, 0, 0, NULL},
 };
 
+/* ch_log: the log lives in the handle's context */
+PyObject *
+CH_get_log(PyObject *self_, void *closure)
+{
+    (void)closure;
+    PyObject *log = ch_log((CHOb *)self_);
+    Py_INCREF(log);
+    return log;
+}
+
 PyGetSetDef CH_getset[] = {
+    {(char *)"ch_log", CH_get_log, NULL, NULL, NULL},
     {(char *)"readable", CH_get_misused, NULL, NULL, NULL},
     {(char *)"writable", CH_get_misused, NULL, NULL, NULL},
     {NULL, NULL, NULL, NULL, NULL},
@@ -3664,8 +3806,17 @@ ch_entry_fn
 ch_direct_entry(FSMOb *self, PyObject *target)
 {
     PyTypeObject *tp = Py_TYPE(self);
+#if CUEBALL_EXACT_TYPES
+    /* every transition of every FSM asks: the registered slot and pool
+     * classes are no handles (checked when they were registered) */
+    if (tp != g_handle_cls &&
+        (tp == g_slot_cls || tp == g_pool_cls ||
+         !PyType_IsSubtype(tp, &CHType)))
+        return NULL;
+#else
     if (!PyType_IsSubtype(tp, &CHType))
         return NULL;
+#endif
     for (int i = 0; i < ch_n_entries; i++) {
         ChEntry *e = &ch_entries[i];
         if (*e->ce_state != target)
@@ -4203,12 +4354,174 @@ typedef struct {
 
 extern PyTypeObject CTType;
 
+/* -- PoolCtx: the pool's claim context (declared with CHOb) ----------- */
+
+PyObject *s_p_counters;          /* "p_counters" */
+extern PyObject *s_p_dead;       /* "p_dead" (SlotDispatch section) */
+extern PyObject *s_p_codel;      /* "p_codel" (ClaimMethod section) */
+extern PyObject *s_p_claim_log;  /* "p_claim_log" */
+
+static int
+PoolCtx_traverse(PyObject *self_, visitproc visit, void *arg)
+{
+    PoolCtx *cx = (PoolCtx *)self_;
+    Py_VISIT((PyObject *)cx->pc_idleq);
+    Py_VISIT((PyObject *)cx->pc_waiters);
+    Py_VISIT((PyObject *)cx->pc_initq);
+    Py_VISIT(cx->pc_counters);
+    Py_VISIT(cx->pc_dead);
+    Py_VISIT((PyObject *)cx->pc_lat);
+    Py_VISIT(cx->pc_log);
+    return 0;
+}
+
+static int
+PoolCtx_clear_(PyObject *self_)
+{
+    PoolCtx *cx = (PoolCtx *)self_;
+    Py_CLEAR(cx->pc_idleq);
+    Py_CLEAR(cx->pc_waiters);
+    Py_CLEAR(cx->pc_initq);
+    Py_CLEAR(cx->pc_counters);
+    Py_CLEAR(cx->pc_dead);
+    Py_CLEAR(cx->pc_lat);
+    Py_CLEAR(cx->pc_log);
+    return 0;
+}
+
+static void
+PoolCtx_dealloc(PyObject *self_)
+{
+    PyObject_GC_UnTrack(self_);
+    PoolCtx_clear_(self_);
+    PyObject_GC_Del(self_);
+}
+
+PyTypeObject PoolCtxType = {
+    PyVarObject_HEAD_INIT(NULL, 0)
+    "cueball_amd._speed._PoolCtx",
+    sizeof(PoolCtx),
+};
+
+static void
+poolctx_type_init(void)
+{
+    PoolCtxType.tp_dealloc = PoolCtx_dealloc;
+    PoolCtxType.tp_flags = Py_TPFLAGS_DEFAULT | Py_TPFLAGS_HAVE_GC;
+    PoolCtxType.tp_traverse = PoolCtx_traverse;
+    PoolCtxType.tp_clear = PoolCtx_clear_;
+}
+
+static PoolCtx *
+poolctx_alloc(void)
+{
+    PoolCtx *cx = PyObject_GC_New(PoolCtx, &PoolCtxType);
+    if (cx == NULL)
+        return NULL;
+    cx->pc_idleq = cx->pc_waiters = cx->pc_initq = NULL;
+    cx->pc_counters = cx->pc_dead = cx->pc_log = NULL;
+    cx->pc_lat = NULL;
+    cx->pc_no_codel = 0;
+    PyObject_GC_Track((PyObject *)cx);
+    return cx;
+}
+
+PoolCtx *
+pool_ctx_private(PoolCtx *base, PoolLatOb *lat, PyObject *log)
+{
+    PoolCtx *cx = poolctx_alloc();
+    if (cx == NULL)
+        return NULL;
+    if (base != NULL && base->pc_idleq != NULL) {
+        Py_INCREF((PyObject *)base->pc_idleq);
+        cx->pc_idleq = base->pc_idleq;
+        Py_INCREF((PyObject *)base->pc_waiters);
+        cx->pc_waiters = base->pc_waiters;
+        Py_INCREF((PyObject *)base->pc_initq);
+        cx->pc_initq = base->pc_initq;
+    }
+    Py_XINCREF((PyObject *)lat);
+    cx->pc_lat = lat;
+    Py_INCREF(log);
+    cx->pc_log = log;
+    return cx;
+}
+
+/* Read the eight attributes once.  All must be there, with p_counters and
+ * p_dead dicts: anything else is no ConnectionPool and gets no context. */
+static PoolCtx *
+pool_ctx_make(FSMOb *pool)
+{
+    PyObject *names[8] = {s_p_idleq, s_p_waiters, s_p_initq, s_p_counters,
+                          s_p_dead, s_p_lat, s_p_claim_log, s_p_codel};
+    PyObject *v[8] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+    PoolCtx *cx = NULL;
+    int ok = 1;
+    for (int i = 0; i < 8 && ok; i++) {
+        if (_PyObject_LookupAttr((PyObject *)pool, names[i], &v[i]) < 0)
+            PyErr_Clear();
+        ok = v[i] != NULL;
+    }
+    if (ok && PyDict_Check(v[3]) && PyDict_Check(v[4]) &&
+        pool->f_ctx == NULL)          /* the reads may have run code */
+        cx = poolctx_alloc();
+    if (cx != NULL) {
+        if (PyObject_TypeCheck(v[0], &NQueueType) &&
+            PyObject_TypeCheck(v[1], &NQueueType) &&
+            PyObject_TypeCheck(v[2], &NQueueType)) {
+            cx->pc_idleq = (NQueue *)v[0];
+            cx->pc_waiters = (NQueue *)v[1];
+            cx->pc_initq = (NQueue *)v[2];
+            v[0] = v[1] = v[2] = NULL;
+        }
+        cx->pc_counters = v[3];
+        cx->pc_dead = v[4];
+        v[3] = v[4] = NULL;
+        if (Py_TYPE(v[5]) == &PoolLatType) {
+            cx->pc_lat = (PoolLatOb *)v[5];
+            v[5] = NULL;
+        }
+        cx->pc_log = v[6];
+        v[6] = NULL;
+        cx->pc_no_codel = v[7] == Py_None;
+        pool->f_ctx = (PyObject *)cx;
+    } else if (PyErr_Occurred()) {
+        PyErr_Clear();
+    }
+    for (int i = 0; i < 8; i++)
+        Py_XDECREF(v[i]);
+    return (PoolCtx *)pool->f_ctx;
+}
+
+PoolCtx *
+pool_ctx(PyObject *pool)
+{
+    if (!is_fsm(pool))
+        return NULL;
+    PyObject *cx = ((FSMOb *)pool)->f_ctx;
+    if (cx != NULL)
+        return (PoolCtx *)cx;
+    return pool_ctx_make((FSMOb *)pool);
+}
+
 /* cache the pool's queues on the ticket; a pool whose queues are not
  * the native deque leaves them NULL and the ticket permanently
  * delegates to the python slow path */
 static void
 ct_bind_queues(TicketCore *t, PyObject *pool)
 {
+    PoolCtx *cx = pool_ctx(pool);
+    if (cx != NULL) {
+        if (cx->pc_idleq != NULL) {
+            Py_INCREF((PyObject *)cx->pc_idleq);
+            t->ct_idleq = cx->pc_idleq;
+            Py_INCREF((PyObject *)cx->pc_waiters);
+            t->ct_waiters = cx->pc_waiters;
+            Py_INCREF((PyObject *)cx->pc_initq);
+            t->ct_initq = cx->pc_initq;
+        }
+        return;
+    }
     PyObject *iq = PyObject_GetAttr(pool, s_p_idleq);
     PyObject *wq = iq ? PyObject_GetAttr(pool, s_p_waiters) : NULL;
     PyObject *nq = wq ? PyObject_GetAttr(pool, s_p_initq) : NULL;
@@ -4289,7 +4602,6 @@ ct_note_demand(TicketCore *t)
     return 0;
 }
 
-PyObject *s_p_counters;          /* "p_counters" */
 PyObject *s_p_rebal_scheduled;   /* "p_rebal_scheduled" */
 PyObject *s_max_claim_queue;     /* "max-claim-queue" */
 PyObject *s_queued_claim;        /* "queued-claim" */
@@ -4311,7 +4623,14 @@ ct_enqueue_waiter(TicketCore *t)
     if (ct_note_demand(t) < 0)
         return -1;
 
-    PyObject *counters = PyObject_GetAttr(t->ct_pool, s_p_counters);
+    PoolCtx *cx = pool_ctx(t->ct_pool);
+    PyObject *counters;
+    if (cx != NULL) {
+        counters = cx->pc_counters;
+        Py_INCREF(counters);
+    } else {
+        counters = PyObject_GetAttr(t->ct_pool, s_p_counters);
+    }
     if (counters == NULL)
         return -1;
     if (!PyDict_Check(counters)) {
@@ -4421,7 +4740,7 @@ ct_try_next(TicketCore *t)
         Py_DECREF((PyObject *)n);
         if (fsm == NULL)
             continue;
-        if (PyObject_TypeCheck(fsm, &SlotBaseType)) {
+        if (is_slot(fsm)) {
             slot_field_store(&((SlotOb *)fsm)->sl_idleq_node, Py_None);
         } else if (PyObject_SetAttr(fsm, s_p_idleq_node, Py_None) < 0) {
             Py_DECREF(fsm);
@@ -4430,7 +4749,7 @@ ct_try_next(TicketCore *t)
         /* stale entries tolerated: only a slot still in 'idle' is
          * usable (lib/pool.js:934-951) */
         int isidle;
-        if (PyObject_TypeCheck(fsm, &FSMType)) {
+        if (is_fsm(fsm)) {
             PyObject *fs = ((FSMOb *)fsm)->f_state;
             isidle = (fs == s_idle ||
                       (fs != NULL &&
@@ -4467,13 +4786,17 @@ ct_try_next(TicketCore *t)
 static int
 ch_ticket_try_next(CHOb *h)
 {
-    TicketCore v = {h->chb_pool, (PyObject *)h, (NQueue *)h->chb_idleq,
-                    (NQueue *)h->chb_waiters, (NQueue *)h->chb_initq,
-                    h->chb_tk_err_on_empty};
-    /* the pool keeps its queues; the view borrows them and the pool */
+    PoolCtx *cx = h->chb_ctx;
+    if (cx == NULL)
+        return 0;
+    TicketCore v = {h->chb_pool, (PyObject *)h, cx->pc_idleq,
+                    cx->pc_waiters, cx->pc_initq, h->chb_tk_err_on_empty};
+    /* the view borrows the pool and the context with its queues */
     PyObject *pool = v.ct_pool;
     Py_INCREF(pool);
+    Py_INCREF((PyObject *)cx);
     int r = ct_try_next(&v);
+    Py_DECREF((PyObject *)cx);
     Py_DECREF(pool);
     return r;
 }
@@ -4536,11 +4859,11 @@ CT_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
     (void)kwds;
     if (!PyArg_ParseTuple(args, "OOO", &pool, &handle, &err_on_empty))
         return NULL;
-    if (!PyObject_TypeCheck(pool, &FSMType)) {
+    if (!is_fsm(pool)) {
         PyErr_SetString(PyExc_TypeError, "pool must be a native FSM");
         return NULL;
     }
-    if (!PyObject_TypeCheck(handle, &CHType)) {
+    if (!is_handle(handle)) {
         PyErr_SetString(PyExc_TypeError,
                         "handle must be a ClaimHandleBase");
         return NULL;
@@ -4587,12 +4910,19 @@ speed_pool_claim(PyObject *mod, PyObject *const *args, Py_ssize_t nargs)
         return NULL;
     }
     PyObject *pool = args[1];
-    if (!PyObject_TypeCheck(pool, &FSMType)) {
+    if (!is_fsm(pool)) {
         PyErr_SetString(PyExc_TypeError, "pool must be a native FSM");
         return NULL;
     }
     /* counters["claim"] += 1 ("claim" is not a tracked metric event) */
-    PyObject *counters = PyObject_GetAttr(pool, s_p_counters);
+    PoolCtx *cx = pool_ctx(pool);
+    PyObject *counters;
+    if (cx != NULL) {
+        counters = cx->pc_counters;
+        Py_INCREF(counters);
+    } else {
+        counters = PyObject_GetAttr(pool, s_p_counters);
+    }
     if (counters == NULL)
         return NULL;
     if (PyDict_Check(counters)) {
@@ -4669,7 +4999,7 @@ speed_claim_fast(PyObject *mod, PyObject *const *args, Py_ssize_t nargs)
         return NULL;
     }
     PyObject *pool = args[1];
-    if (!PyObject_TypeCheck(pool, &FSMType)) {
+    if (!is_fsm(pool)) {
         PyErr_SetString(PyExc_TypeError, "pool must be a native FSM");
         return NULL;
     }
@@ -4694,11 +5024,15 @@ speed_claim_fast(PyObject *mod, PyObject *const *args, Py_ssize_t nargs)
      * and nothing registered */
     {
         CHOb *h = (CHOb *)handle;
-        TicketCore q = {NULL, NULL, NULL, NULL, NULL, 0};
-        ct_bind_queues(&q, pool);
-        Py_XSETREF(h->chb_idleq, (PyObject *)q.ct_idleq);
-        Py_XSETREF(h->chb_waiters, (PyObject *)q.ct_waiters);
-        Py_XSETREF(h->chb_initq, (PyObject *)q.ct_initq);
+        if (pool_ctx(pool) == NULL) {
+            /* a pool without a context: the handle's private one gets
+             * whatever queues the attributes give */
+            TicketCore q = {NULL, NULL, NULL, NULL, NULL, 0};
+            ct_bind_queues(&q, pool);
+            Py_XSETREF(h->chb_ctx->pc_idleq, q.ct_idleq);
+            Py_XSETREF(h->chb_ctx->pc_waiters, q.ct_waiters);
+            Py_XSETREF(h->chb_ctx->pc_initq, q.ct_initq);
+        }
         h->chb_tk_err_on_empty = err_on_empty;
         h->chb_tk_on = 1;
     }
@@ -4859,7 +5193,7 @@ extern PyTypeObject KitCbType;
 PyObject *
 slotkit_conn_err_cb(PyObject *slot, PyObject *handle)
 {
-    if (slot == NULL || !PyObject_TypeCheck(slot, &SlotBaseType))
+    if (slot == NULL || !is_slot(slot))
         return NULL;
     PyObject *kit = ((FSMOb *)slot)->f_fastkit;
     if (kit == NULL || Py_TYPE(kit) != &SlotKitType ||
@@ -4975,7 +5309,7 @@ kitcb_fire(PyObject *self_, PyObject *st)
          * and removed when that state is left, so the handle is the
          * slot's */
         PyObject *hdl = ((SlotOb *)k->k_slot)->sl_handle;
-        if (hdl == NULL || !PyObject_TypeCheck(hdl, &CHType))
+        if (hdl == NULL || !is_handle(hdl))
             break;
         Py_INCREF(hdl);
         PyObject *res = conn_err_fire((CHOb *)hdl,
@@ -5064,7 +5398,7 @@ kit_state_busy(SlotKit *k)
 #endif
     int armed = 0;
 #if CUEBALL_HANDLE_HOOKS
-    if (PyObject_TypeCheck(hdl, &CHType)) {
+    if (is_handle(hdl)) {
         /* the handle calls back by itself (ch_slot_hook), in the place
          * a listener registered now would have */
         CHOb *h = (CHOb *)hdl;
@@ -5242,7 +5576,7 @@ ch_slot_hook(CHOb *h, PyObject *st)
 {
     PyObject *slot = h->chb_slot;
     if (h->chb_bk_serial == 0 || slot == NULL ||
-        !PyObject_TypeCheck(slot, &SlotBaseType))
+        !is_slot(slot))
         return 0;
     PyObject *kit_ = ((FSMOb *)slot)->f_fastkit;
     if (kit_ == NULL || Py_TYPE(kit_) != &SlotKitType)
@@ -5730,7 +6064,7 @@ slotdispatch_run(PyObject *self_, PyObject *st)
             PyObject *hdl = so->sl_handle;
             int pinger = 0;
             if (hdl != NULL && hdl != Py_None &&
-                PyObject_TypeCheck(hdl, &CHType))
+                is_handle(hdl))
                 pinger = ((CHOb *)hdl)->chb_pinger;
             if (!pinger)
                 Py_RETURN_NONE;
@@ -5744,7 +6078,14 @@ slotdispatch_run(PyObject *self_, PyObject *st)
         (st == s_idle ||
          (PyUnicode_Check(st) &&
           PyUnicode_Compare(st, s_idle) == 0))) {
-        PyObject *dead = PyObject_GetAttr(d->sd_pool, s_p_dead);
+        PoolCtx *cx = pool_ctx(d->sd_pool);
+        PyObject *dead;
+        if (cx != NULL) {
+            dead = cx->pc_dead;
+            Py_INCREF(dead);
+        } else {
+            dead = PyObject_GetAttr(d->sd_pool, s_p_dead);
+        }
         if (dead == NULL)
             return NULL;
         int isdead = PyDict_Check(dead) ?
@@ -5817,7 +6158,7 @@ slotdispatch_run(PyObject *self_, PyObject *st)
             PyObject *hdl = nqueue_shift_value(d->sd_waiters);
             if (hdl == NULL)
                 return NULL;
-            if (!PyObject_TypeCheck(hdl, &CHType)) {
+            if (!is_handle(hdl)) {
                 Py_DECREF(hdl);
                 continue;
             }
@@ -5930,7 +6271,7 @@ SlotDispatch_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
     if (!PyArg_ParseTuple(args, "OOOO", &pool, &fsm, &key, &has_codel))
         return NULL;
     if (!PyObject_TypeCheck(pool, &EmitterType) ||
-        !PyObject_TypeCheck(fsm, &SlotBaseType)) {
+        !is_slot(fsm)) {
         PyErr_SetString(PyExc_TypeError,
                         "SlotDispatch(pool, slot, key, has_codel)");
         return NULL;
@@ -6024,8 +6365,8 @@ SlotKit_new(PyTypeObject *type, PyObject *args, PyObject *kwds)
     (void)kwds;
     if (!PyArg_ParseTuple(args, "OO", &slot, &smgr))
         return NULL;
-    if (!PyObject_TypeCheck(slot, &SlotBaseType) ||
-        !PyObject_TypeCheck(smgr, &FSMType)) {
+    if (!is_slot(slot) ||
+        !is_fsm(smgr)) {
         PyErr_SetString(PyExc_TypeError,
                         "SlotKit(slot, smgr): a SlotBase and a native "
                         "FSM required");
@@ -6143,12 +6484,24 @@ ClaimMethod_vectorcall(PyObject *self_, PyObject *const *args,
         if (cb != Py_None &&
             (opt == Py_None ||
              (PyDict_CheckExact(opt) && PyDict_GET_SIZE(opt) == 0)) &&
-            PyObject_TypeCheck(pool, &FSMType)) {
+            is_fsm(pool)) {
             PyObject *pst = ((FSMOb *)pool)->f_state;
             int open = pst != NULL &&
                 (pst == s_running_st ||
                  PyUnicode_Compare(pst, s_running_st) == 0 ||
                  PyUnicode_CompareWithASCIIString(pst, "starting") == 0);
+            PoolCtx *cx = open ? pool_ctx(pool) : NULL;
+            if (cx != NULL) {
+                if (cx->pc_no_codel) {
+                    PyObject *pargs[5] = {cm->cm_handle_cls, pool, cb,
+                                          cx->pc_log,
+                                          ((FSMOb *)pool)->f_loop};
+                    return speed_pool_claim(NULL, pargs, 5);
+                }
+                return PyObject_Vectorcall(cm->cm_func, args, nargsf,
+                                           kwnames);
+            }
+            /* no context (not a ConnectionPool): the attributes */
             PyObject *codel = open ? PyObject_GetAttr(pool, s_p_codel)
                                    : NULL;
             if (open && codel == NULL)
@@ -6279,6 +6632,45 @@ speed_claim_method(PyObject *mod, PyObject *const *args, Py_ssize_t nargs)
 #endif
 }
 
+/* _set_cycle_classes(handle_cls, slot_cls, pool_cls): the Python classes
+ * whose instances walk the claim cycle, for the exact-type tests
+ * (is_handle, is_slot, is_fsm).  None leaves a class as it is. */
+static PyObject *
+speed_set_cycle_classes(PyObject *mod, PyObject *const *args,
+                        Py_ssize_t nargs)
+{
+    (void)mod;
+    if (nargs != 3) {
+        PyErr_SetString(PyExc_TypeError,
+                        "_set_cycle_classes(handle_cls, slot_cls, pool_cls)");
+        return NULL;
+    }
+    PyTypeObject *bases[3] = {&CHType, &SlotBaseType, &FSMType};
+    PyTypeObject **dst[3] = {&g_handle_cls, &g_slot_cls, &g_pool_cls};
+    for (int i = 0; i < 3; i++) {
+        if (args[i] == Py_None)
+            continue;
+        PyTypeObject *cls = (PyTypeObject *)args[i];
+        if (!PyType_Check(args[i]) || !PyType_IsSubtype(cls, bases[i]) ||
+            (i > 0 && PyType_IsSubtype(cls, &CHType)) ||
+            (i == 2 && PyType_IsSubtype(cls, &SlotBaseType))) {
+            PyErr_SetString(PyExc_TypeError,
+                "_set_cycle_classes: a ClaimHandleBase, a SlotBase and a "
+                "plain FSM subclass required");
+            return NULL;
+        }
+    }
+    for (int i = 0; i < 3; i++) {
+        if (args[i] == Py_None)
+            continue;
+        Py_INCREF(args[i]);
+        PyTypeObject *old = *dst[i];
+        *dst[i] = (PyTypeObject *)args[i];
+        Py_XDECREF((PyObject *)old);
+    }
+    Py_RETURN_NONE;
+}
+
 PyObject *
 speed_set_tracer(PyObject *mod, PyObject *fn)
 {
@@ -6311,6 +6703,9 @@ PyMethodDef speed_methods[] = {
      METH_FASTCALL, NULL},
     {"claim_method", (PyCFunction)(void (*)(void))speed_claim_method,
      METH_FASTCALL, NULL},
+    {"_set_cycle_classes",
+     (PyCFunction)(void (*)(void))speed_set_cycle_classes, METH_FASTCALL,
+     NULL},
     {NULL, NULL, 0, NULL},
 };
 
@@ -6407,6 +6802,7 @@ PyInit__speed(void)
     s_rebalance = PyUnicode_InternFromString("rebalance");
     s_set_unwanted = PyUnicode_InternFromString("set_unwanted");
     queue_types_init();
+    poolctx_type_init();
     ct_type_init();
     slotkit_types_init();
     codel_type_init();
@@ -6431,6 +6827,7 @@ PyInit__speed(void)
         PyType_Ready(&SlotBaseType) < 0 ||
         PyType_Ready(&QNodeType) < 0 ||
         PyType_Ready(&NQueueType) < 0 ||
+        PyType_Ready(&PoolCtxType) < 0 ||
         PyType_Ready(&CTType) < 0 ||
         PyType_Ready(&KitCbType) < 0 ||
         PyType_Ready(&SlotKitType) < 0 ||

@@ -1056,6 +1056,12 @@ class ConnectionSlotFSM(_SlotFSMBase):
             raise FSMError("smgr must be stopped")
 
 
+if _native_count is not None:
+    # the native core tests for these two classes by identity before it
+    # walks an MRO (cueball_amd/_native/speed.cpp, is_handle/is_slot)
+    _speed_mod._set_cycle_classes(ClaimHandle, ConnectionSlotFSM, None)
+
+
 def _do_ping_check(fsm: ConnectionSlotFSM, checker: Callable) -> None:
     """Health-check an idle slot: claim it internally and run the checker
     (lib/connection-fsm.js:1101-1127)."""

@@ -1822,3 +1822,5 @@ if _native_pool_claim is not None:
     from ._speed import claim_method as _claim_method
     ConnectionPool.claim = _claim_method(  # type: ignore[assignment]
         ConnectionPool.__dict__["claim"], ClaimHandle)
+    from ._speed import _set_cycle_classes
+    _set_cycle_classes(None, None, ConnectionPool)
