@@ -37,7 +37,26 @@
  *                         busy and idle states are hooks of the emission
  *   CUEBALL_LAZY_SCOPES   a transition's scope is made when first asked for
  *   CUEBALL_VECTORCALL    the core's own callables take vectorcall, and
- *                         ConnectionPool.claim has a native entry */
+ *                         ConnectionPool.claim has a native entry
+ * Per-claim lookups whose answer is the same on every claim
+ * (profiles/claim_cycle_lookups.md):
+ *   CUEBALL_LEAK_TAG      the leak detector's cached counts are confirmed
+ *                         by the event table's version, not by four lookups
+ *   CUEBALL_OWN_CONN_ERR  the claimed handle registers and removes its
+ *                         connection-error listener itself, without a scope */
+#ifndef CUEBALL_LEAK_TAG
+#define CUEBALL_LEAK_TAG 1
+#endif
+#ifndef CUEBALL_OWN_CONN_ERR
+#define CUEBALL_OWN_CONN_ERR 1
+#endif
+/* dicts carry a version that moves on every change of the dict itself
+ * (not of its values' contents) up to CPython 3.11; later versions keep
+ * the four lookups */
+#if CUEBALL_LEAK_TAG && PY_VERSION_HEX >= 0x030C0000
+#undef CUEBALL_LEAK_TAG
+#define CUEBALL_LEAK_TAG 0
+#endif
 #ifndef CUEBALL_HANDLE_HOOKS
 #define CUEBALL_HANDLE_HOOKS 1
 #endif
@@ -110,11 +129,21 @@ typedef struct {
     /* leak-detector cache (see emitter_leak_counts): ev_gen moves on
      * every add/remove of a listener the detector could count */
     unsigned long ev_gen;
-    unsigned long ev_lk_gen;    /* ev_gen the cache was filled at */
-    long ev_lk_cnt[4];          /* counted listeners per leak event */
-    Py_ssize_t ev_lk_len[4];    /* list lengths the counts belong to */
-    int ev_lk_ok;
+    struct LeakCache *ev_lk;    /* NULL until the detector first counts:
+                                 * only claimed connections have one, so
+                                 * the other emitters (every claim handle
+                                 * is one) do not carry its fields */
 } Emitter;
+
+struct LeakCache {
+    int lk_ok;
+    unsigned long lk_gen;       /* ev_gen the cache was filled at */
+    long lk_cnt[4];             /* counted listeners per leak event */
+    Py_ssize_t lk_len[4];       /* list lengths the counts belong to */
+    uint64_t lk_ver;            /* ev_events' version it was filled at */
+    PyObject *lk_list[4];       /* the lists the lengths were read from,
+                                 * owned, NULL where the table had none */
+};
 
 extern PyTypeObject EmitterType;
 extern PyTypeObject ConnErrCbType;
@@ -184,13 +213,35 @@ Emitter_traverse(PyObject *self_, visitproc visit, void *arg)
     Emitter *self = (Emitter *)self_;
     Py_VISIT(self->ev_events);
     Py_VISIT(self->ev_dict);
+    if (self->ev_lk != NULL)
+        for (int i = 0; i < 4; i++)
+            Py_VISIT(self->ev_lk->lk_list[i]);
     return 0;
+}
+
+/* forget the leak detector's cached counts and the lists they hold */
+static void
+emitter_lk_drop(Emitter *self)
+{
+    LeakCache *lk = self->ev_lk;
+    if (lk == NULL)
+        return;
+    lk->lk_ok = 0;
+    for (int i = 0; i < 4; i++)
+        Py_CLEAR(lk->lk_list[i]);
 }
 
 int
 Emitter_clear_(PyObject *self_)
 {
     Emitter *self = (Emitter *)self_;
+    LeakCache *lk = self->ev_lk;
+    if (lk != NULL) {
+        self->ev_lk = NULL;
+        for (int i = 0; i < 4; i++)
+            Py_CLEAR(lk->lk_list[i]);
+        PyMem_Free(lk);
+    }
     Py_CLEAR(self->ev_events);
     Py_CLEAR(self->ev_dict);
     return 0;
@@ -639,8 +690,8 @@ typedef struct {
 extern PyTypeObject ScopeType;
 
 /* Freed scopes are kept for the next state that asks for one (see
- * fsm_need_scope; of the six states of a claim cycle only the handle's
- * `claimed` does). */
+ * fsm_need_scope; of the six states of a claim cycle none does, unless
+ * the handle's `claimed` is entered with CUEBALL_OWN_CONN_ERR off). */
 #define SCOPE_FREELIST_MAX 32
 Scope *scope_freelist[SCOPE_FREELIST_MAX];
 int scope_freelist_n = 0;
@@ -1101,6 +1152,9 @@ struct FSMOb {
                                  * claim cycle reads of it (pool_ctx) */
     int f_entering;
     int f_emit_scheduled;
+    int f_own_reg;              /* a claim handle in `claimed` that holds its
+                                 * connection's error registration itself
+                                 * (ch_drop_conn_err) */
 };
 
 /* forward decl (SlotKit lives after the CH/Queue sections);
@@ -1132,6 +1186,9 @@ extern PyObject *t_empty;
 extern PyTypeObject CHType;
 extern PyTypeObject CTType;
 void ch_terminal_cleanup(FSMOb *self);
+/* leaving `claimed`: remove the error listener the handle registered on
+ * its connection without a scope (f_own_reg) */
+int ch_drop_conn_err(FSMOb *self);
 
 /* the claim handle's C state entry for `target`, if the type of `self`
  * still resolves that entry to it (no Python override); else NULL */
@@ -1569,6 +1626,10 @@ fsm_enter_loop(FSMOb *self, PyObject *state)
                 return -1;
             }
             Py_DECREF(r);
+        }
+        if (self->f_own_reg && ch_drop_conn_err(self) < 0) {
+            Py_DECREF(target);
+            return -1;
         }
         Py_CLEAR(self->f_valid);
         Py_INCREF(target);
@@ -2691,6 +2752,9 @@ typedef struct {
     PoolCtx *chb_ctx;       /* owned: the pool's context or a private one
                              * (latency recorder, log, queues); NULL
                              * before _setup */
+    PyObject *chb_err_conn; /* while base.f_own_reg: the connection and the */
+    PyObject *chb_err_cb;   /* callback of the handle's own `error`
+                             * registration, owned */
     double chb_claim_timeout;
     double chb_started;
     double chb_claimed_at;  /* valid while chb_lat_open */
@@ -2800,16 +2864,50 @@ c_count_listeners(PyObject *emitter, PyObject *event)
  * In steady state the listeners of a pooled connection are the same
  * from one claim to the next, so the counts are cached on the emitter,
  * tagged with its generation and the four list lengths (the lengths
- * catch a list changed behind the emitter's back, through _events);
- * with the tag intact this costs four dict lookups instead of a walk
- * over every listener with two attribute lookups each. */
+ * catch a list changed behind the emitter's back, through _events).
+ * Which lists the table holds is confirmed by the table's own version,
+ * which moves when a key is added, deleted or given another value and
+ * stays when a list's contents change; the cached lists are then asked
+ * for their lengths.  With the tag intact this costs no lookup at all,
+ * instead of a walk over every listener with two attribute lookups
+ * each.  Without the version (CUEBALL_LEAK_TAG=0, or a CPython whose
+ * dicts have none) the lists are looked up, four times per call. */
+static inline Py_ssize_t
+leak_list_len(PyObject *ls)
+{
+    return (ls != NULL && PyList_Check(ls)) ? PyList_GET_SIZE(ls) : -1;
+}
+
 int
 emitter_leak_counts(PyObject *conn, long out[4])
 {
     if (!PyObject_TypeCheck(conn, &EmitterType))
         return -2;
     Emitter *em = (Emitter *)conn;
+    LeakCache *lk = em->ev_lk;
+#if CUEBALL_LEAK_TAG
+    if (lk != NULL && lk->lk_ok && lk->lk_gen == em->ev_gen &&
+        em->ev_events != NULL &&
+        lk->lk_ver == ((PyDictObject *)em->ev_events)->ma_version_tag) {
+        int same = 1;
+        for (int i = 0; i < 4; i++) {
+            same &= (leak_list_len(lk->lk_list[i]) == lk->lk_len[i]);
+        }
+        if (same) {
+            memcpy(out, lk->lk_cnt, sizeof(lk->lk_cnt));
+            return 0;
+        }
+    }
+#endif
     Py_ssize_t lens[4];
+    PyObject *lists[4];
+    uint64_t ver = 0;
+#if CUEBALL_LEAK_TAG
+    /* read before the lookups: a version that moves during them (a key's
+     * __eq__ can run code) makes the next call look again */
+    if (em->ev_events != NULL)
+        ver = ((PyDictObject *)em->ev_events)->ma_version_tag;
+#endif
     for (int i = 0; i < 4; i++) {
         PyObject *ls = NULL;
         if (em->ev_events != NULL) {
@@ -2817,31 +2915,50 @@ emitter_leak_counts(PyObject *conn, long out[4])
             if (ls == NULL && PyErr_Occurred())
                 return -1;
         }
-        lens[i] = (ls != NULL && PyList_Check(ls)) ? PyList_GET_SIZE(ls)
-                                                   : -1;
+        lists[i] = ls;
+        lens[i] = leak_list_len(ls);
     }
-    if (em->ev_lk_ok && em->ev_lk_gen == em->ev_gen &&
-        memcmp(lens, em->ev_lk_len, sizeof(lens)) == 0) {
-        memcpy(out, em->ev_lk_cnt, sizeof(em->ev_lk_cnt));
+    lk = em->ev_lk;
+    if (lk != NULL && lk->lk_ok && lk->lk_gen == em->ev_gen &&
+        memcmp(lens, lk->lk_len, sizeof(lens)) == 0 &&
+        memcmp(lists, lk->lk_list, sizeof(lists)) == 0) {
+        lk->lk_ver = ver;
+        memcpy(out, lk->lk_cnt, sizeof(lk->lk_cnt));
         return 0;
     }
     unsigned long gen = em->ev_gen;
-    for (int i = 0; i < 4; i++) {
+    for (int i = 0; i < 4; i++)
+        Py_XINCREF(lists[i]);
+    int failed = 0;
+    for (int i = 0; i < 4 && !failed; i++) {
         long c = c_count_listeners(conn, s_leak_events[i]);
         if (c < 0)
-            return -1;
+            failed = 1;
         out[i] = c;
     }
     /* counting reads attributes of the listeners, which may run code:
      * keep the result only if no listener came or went meanwhile */
-    em->ev_lk_ok = 0;
-    if (gen == em->ev_gen) {
-        memcpy(em->ev_lk_cnt, out, sizeof(em->ev_lk_cnt));
-        memcpy(em->ev_lk_len, lens, sizeof(lens));
-        em->ev_lk_gen = gen;
-        em->ev_lk_ok = 1;
+    emitter_lk_drop(em);
+    lk = em->ev_lk;
+    if (!failed && lk == NULL && em->ev_events != NULL) {
+        lk = (LeakCache *)PyMem_Calloc(1, sizeof(LeakCache));
+        em->ev_lk = lk;     /* no memory: counted again next time */
     }
-    return 0;
+    if (!failed && lk != NULL && !lk->lk_ok && gen == em->ev_gen &&
+        em->ev_events != NULL) {
+        memcpy(lk->lk_cnt, out, sizeof(lk->lk_cnt));
+        memcpy(lk->lk_len, lens, sizeof(lens));
+        for (int i = 0; i < 4; i++) {
+            Py_XSETREF(lk->lk_list[i], lists[i]);
+            lists[i] = NULL;
+        }
+        lk->lk_ver = ver;
+        lk->lk_gen = gen;
+        lk->lk_ok = 1;
+    }
+    for (int i = 0; i < 4; i++)
+        Py_XDECREF(lists[i]);
+    return failed ? -1 : 0;
 }
 
 /* claimed-state conn-error listener: raise if the user has no error
@@ -3317,18 +3434,43 @@ CH_state_claimed(PyObject *self_, PyObject *scope)
         PyObject_GC_Track((PyObject *)nec);
         ec = (PyObject *)nec;
     }
-    if (scope == NULL)
-        scope = (PyObject *)fsm_need_scope(&self->base);
-    if (scope == NULL) {
+    PyObject *r;
+#if CUEBALL_OWN_CONN_ERR
+    if (scope == NULL && !self->base.f_own_reg) {
+        /* entered natively: this is the state's only registration, so
+         * the handle keeps it itself and fsm_enter_loop removes it on
+         * the way out, where it would dispose a scope.  Registered as
+         * scope_on_c does. */
+        if (Py_TYPE(conn) == &EmitterType)
+            r = emitter_add((Emitter *)conn, s_error_evt, ec);
+        else
+            r = PyObject_CallMethodObjArgs(conn, s_on, s_error_evt, ec,
+                                           NULL);
+        if (r == NULL) {
+            Py_DECREF(ec);
+            return NULL;
+        }
+        Py_DECREF(r);
+        Py_INCREF(conn);
+        self->chb_err_conn = conn;
+        self->chb_err_cb = ec;      /* our reference */
+        self->base.f_own_reg = 1;
+    } else
+#endif
+    {
+        if (scope == NULL)
+            scope = (PyObject *)fsm_need_scope(&self->base);
+        if (scope == NULL) {
+            Py_DECREF(ec);
+            return NULL;
+        }
+        PyObject *args[3] = {conn, s_error_evt, ec};
+        r = Scope_on(scope, args, 3);
         Py_DECREF(ec);
-        return NULL;
+        if (r == NULL)
+            return NULL;
+        Py_DECREF(r);
     }
-    PyObject *args[3] = {conn, s_error_evt, ec};
-    PyObject *r = Scope_on(scope, args, 3);
-    Py_DECREF(ec);
-    if (r == NULL)
-        return NULL;
-    Py_DECREF(r);
 
     /* the wait ends here, just before the user callback; pinger
      * claims are the pool's own and not counted */
@@ -3349,6 +3491,27 @@ CH_state_claimed(PyObject *self_, PyObject *scope)
         return NULL;
     Py_DECREF(r);
     Py_RETURN_NONE;
+}
+
+int
+ch_drop_conn_err(FSMOb *fsm)
+{
+    CHOb *self = (CHOb *)fsm;
+    /* taken out first: removing a listener can run arbitrary code */
+    PyObject *conn = self->chb_err_conn, *cb = self->chb_err_cb;
+    self->chb_err_conn = self->chb_err_cb = NULL;
+    fsm->f_own_reg = 0;
+    if (conn == NULL || cb == NULL) {
+        Py_XDECREF(conn);
+        Py_XDECREF(cb);
+        return 0;
+    }
+    /* Scope_dispose's rule: through the method if the connection's type
+     * overrides remove_listener or is no native emitter */
+    int rc = scope_unregister(conn, s_error_evt, cb);
+    Py_DECREF(conn);
+    Py_DECREF(cb);
+    return rc;
 }
 
 /* claimed -> released/closed: the lease ends.  Only a handle whose
@@ -3551,6 +3714,8 @@ CH_traverse(PyObject *self_, visitproc visit, void *arg)
     Py_VISIT(self->chb_last_error);
     Py_VISIT(self->chb_waiter_node);
     Py_VISIT((PyObject *)self->chb_ctx);
+    Py_VISIT(self->chb_err_conn);
+    Py_VISIT(self->chb_err_cb);
     return FSM_traverse(self_, visit, arg);
 }
 
@@ -3567,6 +3732,9 @@ CH_clear_(PyObject *self_)
     Py_CLEAR(self->chb_last_error);
     Py_CLEAR(self->chb_waiter_node);
     Py_CLEAR(self->chb_ctx);
+    self->base.f_own_reg = 0;
+    Py_CLEAR(self->chb_err_conn);
+    Py_CLEAR(self->chb_err_cb);
     return FSM_clear_(self_);
 }
 
@@ -6671,6 +6839,33 @@ speed_set_cycle_classes(PyObject *mod, PyObject *const *args,
     Py_RETURN_NONE;
 }
 
+/* _debug_cycle_state(emitter=None): what the per-claim caches hold, for
+ * the tests.  With an emitter, "leak_cache" is None or the cached counts
+ * of its leak detector if they are valid. */
+static PyObject *
+speed_debug_cycle_state(PyObject *mod, PyObject *const *args,
+                        Py_ssize_t nargs)
+{
+    (void)mod;
+    PyObject *lk = Py_None;
+    Py_INCREF(lk);
+    if (nargs >= 1 && PyObject_TypeCheck(args[0], &EmitterType)) {
+        LeakCache *c = ((Emitter *)args[0])->ev_lk;
+        if (c != NULL && c->lk_ok &&
+            c->lk_gen == ((Emitter *)args[0])->ev_gen) {
+            Py_DECREF(lk);
+            lk = Py_BuildValue("(llll)", c->lk_cnt[0], c->lk_cnt[1],
+                               c->lk_cnt[2], c->lk_cnt[3]);
+            if (lk == NULL)
+                return NULL;
+        }
+    }
+    return Py_BuildValue("{s:N,s:i,s:i}",
+                         "leak_cache", lk,
+                         "leak_tag", (int)CUEBALL_LEAK_TAG,
+                         "own_conn_err", (int)CUEBALL_OWN_CONN_ERR);
+}
+
 PyObject *
 speed_set_tracer(PyObject *mod, PyObject *fn)
 {
@@ -6705,6 +6900,9 @@ PyMethodDef speed_methods[] = {
      METH_FASTCALL, NULL},
     {"_set_cycle_classes",
      (PyCFunction)(void (*)(void))speed_set_cycle_classes, METH_FASTCALL,
+     NULL},
+    {"_debug_cycle_state",
+     (PyCFunction)(void (*)(void))speed_debug_cycle_state, METH_FASTCALL,
      NULL},
     {NULL, NULL, 0, NULL},
 };
