@@ -80,6 +80,9 @@ class Agent(EventEmitter):
     #: host -> hedge.HedgeHost: budget, latency window, counters
     cba_hedge_hosts: Optional[Dict[str, Any]] = None
     _hedge_metrics: Optional[tuple] = None
+    #: the validated ``claimBalancing`` option, likewise; a copy goes
+    #: to every pool
+    cba_balancing: Optional[Dict[str, Any]] = None
 
     def __init__(self, options: Dict[str, Any]) -> None:
         super().__init__()
@@ -155,6 +158,12 @@ class Agent(EventEmitter):
             self.cba_hedge_policy = mod_hedge.HedgePolicy(hedge)
             self.cba_hedge_hosts = {}
             self._register_hedge_metrics()
+
+        # Claim balancing (opt-in) is the pools' business; validated
+        # here so that a bad value fails at construction.
+        balancing = mod_utils.assert_claim_balancing(options)
+        if balancing is not None:
+            self.cba_balancing = balancing
 
         for host in options.get("initialDomains") or ():
             self._add_pool(host, {})
@@ -262,6 +271,8 @@ class Agent(EventEmitter):
             pool_opts["connectionAgeSpread"] = self.cba_conn_age_spread
         if self.cba_outlier is not None:
             pool_opts["outlierDetection"] = dict(self.cba_outlier)
+        if self.cba_balancing is not None:
+            pool_opts["claimBalancing"] = dict(self.cba_balancing)
         if self.cba_ping is not None:
             pool_opts["checkTimeout"] = self.cba_ping_interval or 30000
             pool_opts["checker"] = \
@@ -298,6 +309,10 @@ class Agent(EventEmitter):
         """Per-host ``ConnectionPool.get_outlier_stats()``."""
         return {host: pool.get_outlier_stats()
                 for host, pool in self.pools.items()}
+
+    def get_balancing_stats(self, host: str) -> Dict[str, Any]:
+        """``ConnectionPool.get_balancing_stats()`` of `host`'s pool."""
+        return self._pool_for(host).get_balancing_stats()
 
     def _pool_for(self, host: str) -> ConnectionPool:
         pool = self.pools.get(host)

@@ -23,6 +23,7 @@ import time as mod_time
 import uuid as mod_uuid
 from typing import Any, Callable, Dict, List, Mapping, Optional
 
+from . import balance as mod_balance
 from . import codel as mod_codel
 from . import errors as mod_errors
 from . import latency as mod_latency
@@ -138,6 +139,35 @@ class _AvoidClaimTicket:
             handle.remove_listener("stateChanged", self)
 
 
+class _BalancedClaimTicket:
+    """The ticket of every claim on a pool with ``claimBalancing``: the
+    Python path once more, on either runtime, with the balancer choosing
+    among the idle slots (``pool._ticket_balanced``).  The handle and the
+    slot's busy/idle cycle stay what they are."""
+
+    __slots__ = ("pool", "handle", "err_on_empty", "avoid")
+
+    _cueball_ticket = True
+
+    def __init__(self, pool: "ConnectionPool", handle: ClaimHandle,
+                 err_on_empty: bool, avoid: Optional[frozenset]) -> None:
+        self.pool = pool
+        self.handle = handle
+        self.err_on_empty = err_on_empty
+        self.avoid = avoid
+
+    def __call__(self, st: str) -> None:
+        handle = self.handle
+        if handle is None:
+            return
+        if st == "waiting":
+            self.pool._ticket_balanced(handle, self.err_on_empty,
+                                       self.avoid)
+        elif st in ("released", "closed", "cancelled", "failed"):
+            self.handle = None
+            handle.remove_listener("stateChanged", self)
+
+
 _NativeClaimTicket = None
 _native_claim_fast = None
 _native_pool_claim = None
@@ -237,6 +267,23 @@ class ConnectionPool(FSM):
     #: slot -> "error" | "closed": how its current socket ended
     p_od_sock: Optional[Dict[Any, str]] = None
     _od_gauge = None
+
+    # Claim balancing state, class-level like the rest: a pool without
+    # claimBalancing has none of these in its instance dict, and its
+    # claim() is the class's.
+    #: the validated claimBalancing option, defaults filled in
+    p_lb: Optional[Dict[str, Any]] = None
+    #: key -> balance.BackendLoad; dropped when the resolver removes it
+    p_lb_backends: Optional[Dict[str, Any]] = None
+    #: slot -> (handle, load) of a slot the ticket handed over, until
+    #: the slot's 'busy' is heard
+    p_lb_handed: Optional[Dict[Any, tuple]] = None
+    #: slot -> (handle, load, start in loop seconds) of the lease seen
+    #: to begin on it
+    p_lb_open: Optional[Dict[Any, tuple]] = None
+    #: slot -> last handle attributed to it (a handle has one lease)
+    p_lb_last: Optional[Dict[Any, Any]] = None
+    _lb_gauges: Optional[tuple] = None
 
     def __init__(self, options: Dict[str, Any]) -> None:
         if not callable(options.get("constructor")):
@@ -402,6 +449,31 @@ class ConnectionPool(FSM):
                 except (AttributeError, ValueError):
                     pass
 
+        # Claim balancing (opt-in): see the "claim balancing" section
+        # below.  Off means not one attribute is set here; on, claim()
+        # itself is replaced on this instance alone.
+        lb = mod_utils.assert_claim_balancing(options)
+        if lb is not None:
+            self.p_lb = lb
+            self.p_lb_backends = {}
+            self.p_lb_handed = {}
+            self.p_lb_open = {}
+            self.p_lb_last = {}
+            self.claim = self._claim_balanced
+            if self._gauge is not None:
+                try:
+                    self._lb_gauges = (
+                        self.p_collector.gauge(
+                            name="cueball_pool_backend_latency_seconds",
+                            help="Lease latency estimate per backend, as "
+                                 "claim balancing sees it"),
+                        self.p_collector.gauge(
+                            name="cueball_pool_backend_outstanding",
+                            help="Connections per backend handed to a "
+                                 "claim or serving a lease"))
+                except (AttributeError, ValueError):
+                    pass
+
         if options.get("resolver") is not None:
             self.p_resolver = options["resolver"]
             self.p_resolver_custom = True
@@ -542,6 +614,8 @@ class ConnectionPool(FSM):
                                 self._gauge_labels)
         if self._od_gauge is not None:
             self._od_gauge.set(len(self.p_od_ejected), self._gauge_labels)
+        if self._lb_gauges is not None:
+            self._lb_publish()
         if self.p_last_rebal_clamped:
             self.rebalance()
 
@@ -594,6 +668,9 @@ class ConnectionPool(FSM):
             ent = self.p_od_ejected.pop(k, None)
             if ent is not None:
                 ent["timer"].cancel()
+        if self.p_lb_backends is not None:
+            # likewise; leases still open keep the record they began on
+            self.p_lb_backends.pop(k, None)
         # Slots unlink themselves (and rebalance) from the stateChanged
         # handler in add_connection once they stop; here we only flag
         # them unwanted (lib/pool.js:300-313).
@@ -1429,6 +1506,296 @@ class ConnectionPool(FSM):
         return {"enabled": self.p_od is not None,
                 "ejected": len(ejected), "backends": out}
 
+    # -- claim balancing -----------------------------------------------------
+    #
+    # Without the option a claim takes the head of the idle queue, and a
+    # released slot goes to its tail: round-robin over idle connections,
+    # whatever their backends take to answer.  With it, the claim's
+    # ticket looks at the idle slots (all of them, or a few drawn at
+    # random) and takes the one whose backend is cheapest by
+    # balance.backend_costs(): its lease latency estimate times the
+    # connections it has in use, plus one.
+    #
+    # Only the choice among idle slots changes.  When nothing is idle
+    # the claim queues like any other, and the first slot to go idle
+    # feeds the head waiter; the balancer has no say there.
+    #
+    # Leases are observed from outside the claim path, by the scheme of
+    # outlier detection above: pinned to their handle when the slot's
+    # 'busy' is heard, timed on the loop's clock from there to the
+    # slot's next state being heard, and judged by what that state is.
+    # A lease that failed leaves no sample, or a backend that fails fast
+    # would look fast: such backends are outlierDetection's business.
+    # Pinger leases are ignored altogether.
+
+    def _lb_record(self, key: str) -> Any:
+        rec = self.p_lb_backends.get(key)
+        if rec is None:
+            rec = mod_balance.BackendLoad(self.p_lb["decayTime"])
+            if key in self.p_backends:
+                self.p_lb_backends[key] = rec
+            # else a slot of a backend that is gone already: counted on
+            # a record that nobody keeps
+        return rec
+
+    def _lb_watch(self, fsm: ConnectionSlotFSM, key: str) -> None:
+        fsm.on("stateChanged",
+               functools.partial(self._lb_slot_changed, fsm, key))
+
+    def _lb_slot_changed(self, fsm: ConnectionSlotFSM, key: str,
+                         st: str) -> None:
+        if st == "busy":
+            handed = self.p_lb_handed.pop(fsm, None)
+            hdl = fsm.csf_handle
+            if hdl is None:
+                hdl = fsm.csf_prev_handle
+            # a claim the slot rejected leaves no handle behind, and
+            # csf_prev_handle is then the lease before: seen already
+            if hdl is None or hdl is self.p_lb_last.get(fsm) or \
+                    hdl.ch_slot is not fsm or hdl._fsm_state not in (
+                        "claimed", "released", "closed"):
+                hdl = None
+            if handed is not None and handed[0] is not hdl:
+                handed[1].outstanding -= 1      # nothing came of it
+                handed = None
+            if hdl is None:
+                return
+            self.p_lb_last[fsm] = hdl
+            if hdl.ch_pinger:
+                return
+            if handed is not None:
+                rec = handed[1]                 # counted by the ticket
+            else:
+                # the lease began by feeding a waiter
+                rec = self._lb_record(key)
+                rec.outstanding += 1
+            self.p_lb_open[fsm] = (hdl, rec, self._loop.time())
+            return
+        ent = self.p_lb_open.pop(fsm, None)
+        if ent is not None:
+            hdl, rec, t0 = ent
+            rec.outstanding -= 1
+            rec.leases += 1
+            if hdl._fsm_state == "closed" or hdl.ch_failure_reported or \
+                    st in ("retrying", "connecting", "failed", "stopped"):
+                rec.failed += 1
+            else:
+                now = self._loop.time()
+                rec.ewma.observe((now - t0) * 1000.0, now * 1000.0)
+        if st == "stopped" or st == "failed":
+            self.p_lb_last.pop(fsm, None)
+            handed = self.p_lb_handed.pop(fsm, None)
+            if handed is not None:
+                handed[1].outstanding -= 1
+
+    def _lb_pick(self, avoid: Optional[frozenset]) -> Optional[tuple]:
+        """Unlink the idle slot the balancer chooses and return it, with
+        whether it was not the first idle slot in queue order; None when
+        nothing is idle.  The queue discipline of _idle_avoiding:
+        stale entries met on the walk are unlinked, idle slots that are
+        passed over stay linked where they are."""
+        entries = list(self.p_idleq)
+        m = len(entries)
+        head = 0
+        while head < m and entries[head]._fsm_state != "idle":
+            fsm = entries[head]
+            fsm.p_idleq_node.remove()
+            fsm.p_idleq_node = None
+            head += 1
+        if head == m:
+            return None
+        first = entries[head]
+        lb = self.p_lb
+        n = lb["choices"]
+        if n != "all" and avoid is None and m - head > n:
+            # the common case of a few choices: no need to look at
+            # every entry
+            cands = self._lb_draw(entries, head, n)
+        else:
+            cands = [first]
+            for fsm in entries[head + 1:]:
+                if fsm._fsm_state == "idle":
+                    cands.append(fsm)
+                else:
+                    fsm.p_idleq_node.remove()
+                    fsm.p_idleq_node = None
+            if avoid is not None:
+                # the avoid filter narrows first, and yields when it
+                # would leave nothing
+                cands = [fsm for fsm in cands
+                         if fsm.csf_backend.get("key") not in avoid] or cands
+            if n != "all" and len(cands) > n:
+                # uniformly, without replacement, still in queue order
+                rng = lb["rng"] or random
+                cands = [cands[i] for i in
+                         sorted(rng.sample(range(len(cands)), n))]
+        fsm = cands[0]
+        if len(cands) > 1:
+            loads = self.p_lb_backends
+            # The cost is the backend's and a tie goes to the earliest:
+            # only the first candidate of each backend can win.  A slot
+            # of a backend that is gone already has no record, and
+            # comes last.
+            firsts: Dict[str, ConnectionSlotFSM] = {}
+            for c in cands:
+                k = c.csf_backend.get("key")
+                if k not in firsts:
+                    firsts[k] = c
+                    self._lb_record(k)
+            if len(firsts) > 1:
+                costs = mod_balance.backend_costs(
+                    loads, self._loop.time() * 1000.0, lb["policy"],
+                    [k for k in firsts if k in loads])
+                fsm = mod_balance.pick(
+                    [(c, costs.get(k, math.inf))
+                     for k, c in firsts.items()])
+        fsm.p_idleq_node.remove()
+        fsm.p_idleq_node = None
+        return fsm, fsm is not first
+
+    def _lb_draw(self, entries: List[ConnectionSlotFSM], head: int,
+                 n: int) -> List[ConnectionSlotFSM]:
+        """`n` of the live slots among ``entries[head:]``, drawn
+        uniformly without replacement (a partial Fisher-Yates shuffle of
+        the positions; a stale entry that is drawn is unlinked and drawn
+        over), in queue order.  ``entries[head]`` is live, so the result
+        is never empty."""
+        rnd = (self.p_lb["rng"] or random).random
+        order = list(range(head, len(entries)))
+        left = len(order)
+        chosen: List[int] = []
+        i = 0
+        while i < left and len(chosen) < n:
+            j = i + int(rnd() * (left - i))
+            order[i], order[j] = order[j], order[i]
+            fsm = entries[order[i]]
+            if fsm._fsm_state == "idle":
+                chosen.append(order[i])
+            else:
+                fsm.p_idleq_node.remove()
+                fsm.p_idleq_node = None
+            i += 1
+        chosen.sort()
+        return [entries[k] for k in chosen]
+
+    def _ticket_balanced(self, handle: ClaimHandle, err_on_empty: bool,
+                         avoid: Optional[frozenset]) -> None:
+        """_ticket_slow with the balancer's choice in place of the head
+        of the idle queue; everything else is _ticket_slow itself."""
+        if handle.is_in_state("waiting") and \
+                self._fsm_state in ("starting", "running"):
+            picked = self._lb_pick(avoid)
+            if picked is not None:
+                fsm, reordered = picked
+                # counted from here, so that a burst of claims in one
+                # loop turn sees its own picks
+                rec = self._lb_record(fsm.csf_backend.get("key"))
+                rec.outstanding += 1
+                handle.try_(fsm)
+                if handle._fsm_state in ("waiting", "cancelled"):
+                    # rejected: the slot's socket was gone already.  The
+                    # handle's 'waiting' brings the ticket back here.
+                    rec.outstanding -= 1
+                else:
+                    self.p_lb_handed[fsm] = (handle, rec)
+                    rec.picked += 1
+                    counters = self.p_counters
+                    counters["balanced-claim"] = \
+                        counters.get("balanced-claim", 0) + 1
+                    if reordered:
+                        counters["balanced-reordered"] = \
+                            counters.get("balanced-reordered", 0) + 1
+                self._note_demand()
+                return
+        # nothing idle (the walk has emptied the queue), or the pool is
+        # on its way out
+        self._ticket_slow(handle, err_on_empty)
+
+    def _claim_balanced(self, options: Any = None,
+                        cb: Optional[Callable] = None):
+        """claim() of a pool with ``claimBalancing`` (installed on the
+        instance): the same options, counters and return values; the
+        handle is the runtime's own, its ticket a _BalancedClaimTicket."""
+        if callable(options) and cb is None:
+            cb = options
+            options = {}
+        options = options or {}
+        if cb is None:
+            raise TypeError("claim() requires a callback")
+        err_on_empty = bool(options.get("errorOnEmpty", False))
+        avoid = options.get("avoidBackends")
+        if avoid is not None:
+            avoid = self._assert_avoid(avoid)
+        if self.p_codel is not None:
+            if options.get("timeout") is not None:
+                raise ValueError("options.timeout not allowed when "
+                                 "targetClaimDelay has been set")
+            timeout = self.p_codel.get_max_idle()
+        elif options.get("timeout") is not None:
+            timeout = options["timeout"]
+        else:
+            timeout = math.inf
+
+        counters = self.p_counters
+        counters["claim"] = counters.get("claim", 0) + 1
+        st = self._fsm_state
+        if st == "stopping" or st == "stopped" or \
+                st == "stopping.backends":
+            return self._claim_shortcircuit(
+                cb, mod_errors.PoolStoppingError(self))
+        if st == "failed":
+            return self._claim_shortcircuit(
+                cb, mod_errors.PoolFailedError(self, self.p_last_error))
+        handle = ClaimHandle.fast(
+            self, mod_utils.maybe_capture_stack_trace(), cb,
+            self.p_claim_log, timeout, self._loop)
+        handle.on("stateChanged",
+                  _BalancedClaimTicket(self, handle, err_on_empty, avoid))
+        return handle
+
+    def _lb_publish(self) -> None:
+        lat_gauge, out_gauge = self._lb_gauges
+        now = self._loop.time() * 1000.0
+        for k, rec in self.p_lb_backends.items():
+            labels = {**self._gauge_labels, "backend": k}
+            out_gauge.set(rec.outstanding, labels)
+            est = rec.ewma.get(now)
+            if est is not None:
+                lat_gauge.set(est / 1000.0, labels)
+
+    def get_balancing_stats(self) -> Dict[str, Any]:
+        """Claim balancing as the pool sees it: ``{"enabled", "policy",
+        "choices", "decayTimeMs", "backends": {key: {"connections",
+        "idle", "outstanding", "leases", "failedLeases", "latencyMs",
+        "cost", "picked"}}}``, one entry per backend the pool knows.
+        ``latencyMs`` is the estimate aged to now, None before the first
+        sample; ``leases`` counts the leases that ended, the failed ones
+        included.  ``{"enabled": False}`` when the pool was created
+        without ``claimBalancing``."""
+        lb = self.p_lb
+        if lb is None:
+            return {"enabled": False}
+        now = self._loop.time() * 1000.0
+        loads = {k: self._lb_record(k) for k in self.p_keys}
+        costs = mod_balance.backend_costs(loads, now, lb["policy"])
+        out: Dict[str, Any] = {}
+        for k, rec in loads.items():
+            conns = self.p_connections.get(k, ())
+            out[k] = {
+                "connections": len(conns),
+                "idle": sum(1 for fsm in conns
+                            if fsm._fsm_state == "idle"),
+                "outstanding": rec.outstanding,
+                "leases": rec.leases,
+                "failedLeases": rec.failed,
+                "latencyMs": rec.ewma.get(now),
+                "cost": costs[k],
+                "picked": rec.picked,
+            }
+        return {"enabled": True, "policy": lb["policy"],
+                "choices": lb["choices"], "decayTimeMs": lb["decayTime"],
+                "backends": out}
+
     # -- slot lifecycle ----------------------------------------------------
     def add_connection(self, key: str) -> None:
         if self.is_in_state("stopping") or self.is_in_state("stopped"):
@@ -1467,6 +1834,8 @@ class ConnectionPool(FSM):
             self._age_watch(fsm)
         if self.p_od is not None:
             self._od_watch(fsm, key)
+        if self.p_lb is not None:
+            self._lb_watch(fsm, key)
         fsm.start()
 
     def _slot_state_changed(self, fsm: ConnectionSlotFSM, key: str,

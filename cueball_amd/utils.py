@@ -316,7 +316,64 @@ def assert_outlier_detection(options: Mapping[str, Any],
     return out
 
 
-RETRY_REASONS = ("reset", "timeout", "status", "claim-failure")
+_BALANCING_KEYS = ("policy", "choices", "decayTime", "rng")
+_BALANCING_POLICIES = ("peakEwma", "leastLoaded")
+
+
+def assert_claim_balancing(options: Mapping[str, Any]
+                           ) -> Optional[Dict[str, Any]]:
+    """Validate ``claimBalancing`` and return it with every default
+    filled in (``rng`` None meaning the ``random`` module), or None
+    when the option is off."""
+    lb = options.get("claimBalancing")
+    if lb is None:
+        return None
+    name = "options.claimBalancing"
+    if not isinstance(lb, Mapping):
+        raise TypeError("%s must be a mapping" % name)
+    extra = set(lb.keys()) - set(_BALANCING_KEYS)
+    if extra:
+        raise ValueError("%s has unknown keys: %r"
+                         % (name, sorted(extra, key=str)))
+
+    policy = lb.get("policy")
+    if policy is None:
+        policy = "peakEwma"
+    if not isinstance(policy, str):
+        raise TypeError("%s.policy must be a string" % name)
+    if policy not in _BALANCING_POLICIES:
+        raise ValueError("%s.policy must be one of %r"
+                         % (name, list(_BALANCING_POLICIES)))
+
+    choices = lb.get("choices")
+    if choices is None:
+        choices = 2
+    if isinstance(choices, str):
+        if choices != "all":
+            raise ValueError('%s.choices must be an int >= 2 or "all"'
+                             % name)
+    elif not isinstance(choices, int) or isinstance(choices, bool):
+        raise TypeError('%s.choices must be an int or "all"' % name)
+    elif choices < 2:
+        raise ValueError('%s.choices must be >= 2 or "all"' % name)
+
+    decay = lb.get("decayTime")
+    if decay is None:
+        decay = 10000
+    if not _num(decay):
+        raise TypeError("%s.decayTime must be a number" % name)
+    if not math.isfinite(decay) or decay <= 0:
+        raise ValueError("%s.decayTime must be finite and > 0" % name)
+
+    rng = lb.get("rng")
+    if rng is not None and not isinstance(rng, random.Random):
+        raise TypeError("%s.rng must be a random.Random" % name)
+
+    return {"policy": policy, "choices": choices, "decayTime": decay,
+            "rng": rng}
+
+
+RETRY_REASONS =("reset", "timeout", "status", "claim-failure")
 
 _RETRY_KEYS = ("maxRetries", "retryOn", "retryStatuses", "methods",
                "perTryTimeout", "totalTimeout", "delay", "maxDelay",
