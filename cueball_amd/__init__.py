@@ -11,8 +11,8 @@ FSM runtime and DNS protocol engine.
 from .codel import ControlledDelay
 from .connection import TcpConnection, tcp_constructor
 from .connection_fsm import ClaimHandle, ConnectionSlotFSM
-from .errors import (ClaimHandleMisusedError, ClaimTimeoutError,
-                     ConnectionClosedError, ConnectionError_,
+from .errors import (ClaimHandleMisusedError, ClaimQueueFullError,
+                     ClaimTimeoutError, ConnectionClosedError, ConnectionError_,
                      ConnectionTimeoutError, CueballError, NoBackendsError,
                      PoolFailedError, PoolStoppingError,
                      RequestTimeoutError)
@@ -60,6 +60,7 @@ __all__ = [
     "NoBackendsError",
     "PoolFailedError",
     "PoolStoppingError",
+    "ClaimQueueFullError",
     "RequestTimeoutError",
     "ConnectionError_",
     "ConnectionTimeoutError",

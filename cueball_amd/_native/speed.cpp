@@ -4299,6 +4299,77 @@ NQueue_push(PyObject *self_, PyObject *value)
     return (PyObject *)nqueue_push((NQueue *)self_, value);
 }
 
+/* Link a new node directly behind `prev`, or at the head when `prev`
+ * is NULL: the refs of nqueue_push (one for the list, one returned). */
+static QNode *
+nqueue_link_after(NQueue *q, QNode *prev, PyObject *value)
+{
+    QNode *n = PyObject_GC_New(QNode, &QNodeType);
+    if (n == NULL)
+        return NULL;
+    QNode *nxt = prev != NULL ? prev->q_next : q->q_first;
+    Py_INCREF(value);
+    n->value = value;
+    n->q_prev = prev;
+    n->q_next = nxt;
+    n->q_queue = q;
+    PyObject_GC_Track((PyObject *)n);
+    if (prev != NULL)
+        prev->q_next = n;
+    else
+        q->q_first = n;
+    if (nxt != NULL)
+        nxt->q_prev = n;
+    else
+        q->q_last = n;
+    q->q_len++;
+    Py_INCREF((PyObject *)n);   /* the list's ref */
+    return n;                   /* caller's ref (from New) */
+}
+
+static PyObject *
+NQueue_unshift(PyObject *self_, PyObject *value)
+{
+    return (PyObject *)nqueue_link_after((NQueue *)self_, NULL, value);
+}
+
+static PyObject *
+NQueue_insert_after(PyObject *self_, PyObject *const *args,
+                    Py_ssize_t nargs)
+{
+    NQueue *q = (NQueue *)self_;
+    if (nargs != 2) {
+        PyErr_SetString(PyExc_TypeError,
+                        "Queue.insert_after(node, value)");
+        return NULL;
+    }
+    /* q_queue is set exactly while the node is linked */
+    if (!PyObject_TypeCheck(args[0], &QNodeType) ||
+        ((QNode *)args[0])->q_queue != q) {
+        PyErr_SetString(PyExc_ValueError,
+                        "Queue.insert_after() needs a node linked in "
+                        "this queue");
+        return NULL;
+    }
+    return (PyObject *)nqueue_link_after(q, (QNode *)args[0], args[1]);
+}
+
+static PyObject *
+NQueue_peek_last(PyObject *self_, PyObject *noargs)
+{
+    NQueue *q = (NQueue *)self_;
+    (void)noargs;
+    if (q->q_last == NULL) {
+        PyErr_SetString(PyExc_IndexError, "peek_last from empty Queue");
+        return NULL;
+    }
+    PyObject *v = q->q_last->value;
+    if (v == NULL)
+        Py_RETURN_NONE;
+    Py_INCREF(v);
+    return v;
+}
+
 static PyObject *
 NQueue_shift(PyObject *self_, PyObject *noargs)
 {
@@ -4444,6 +4515,10 @@ static PyMethodDef NQueue_methods[] = {
     {"peek", NQueue_peek, METH_NOARGS, NULL},
     {"is_empty", NQueue_is_empty, METH_NOARGS, NULL},
     {"for_each", NQueue_for_each, METH_O, NULL},
+    {"unshift", NQueue_unshift, METH_O, NULL},
+    {"insert_after", (PyCFunction)(void (*)(void))NQueue_insert_after,
+     METH_FASTCALL, NULL},
+    {"peek_last", NQueue_peek_last, METH_NOARGS, NULL},
     {NULL, NULL, 0, NULL},
 };
 

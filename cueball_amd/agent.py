@@ -83,6 +83,8 @@ class Agent(EventEmitter):
     #: the validated ``claimBalancing`` option, likewise; a copy goes
     #: to every pool
     cba_balancing: Optional[Dict[str, Any]] = None
+    #: the validated ``claimQueue`` option, likewise
+    cba_queue: Optional[Dict[str, Any]] = None
 
     def __init__(self, options: Dict[str, Any]) -> None:
         super().__init__()
@@ -164,6 +166,10 @@ class Agent(EventEmitter):
         balancing = mod_utils.assert_claim_balancing(options)
         if balancing is not None:
             self.cba_balancing = balancing
+        # The claim queue (opt-in), likewise.
+        queue = mod_utils.assert_claim_queue(options)
+        if queue is not None:
+            self.cba_queue = queue
 
         for host in options.get("initialDomains") or ():
             self._add_pool(host, {})
@@ -273,6 +279,8 @@ class Agent(EventEmitter):
             pool_opts["outlierDetection"] = dict(self.cba_outlier)
         if self.cba_balancing is not None:
             pool_opts["claimBalancing"] = dict(self.cba_balancing)
+        if self.cba_queue is not None:
+            pool_opts["claimQueue"] = dict(self.cba_queue)
         if self.cba_ping is not None:
             pool_opts["checkTimeout"] = self.cba_ping_interval or 30000
             pool_opts["checker"] = \
@@ -313,6 +321,10 @@ class Agent(EventEmitter):
     def get_balancing_stats(self, host: str) -> Dict[str, Any]:
         """``ConnectionPool.get_balancing_stats()`` of `host`'s pool."""
         return self._pool_for(host).get_balancing_stats()
+
+    def get_queue_stats(self, host: str) -> Dict[str, Any]:
+        """``ConnectionPool.get_queue_stats()`` of `host`'s pool."""
+        return self._pool_for(host).get_queue_stats()
 
     def _pool_for(self, host: str) -> ConnectionPool:
         pool = self.pools.get(host)
@@ -424,8 +436,9 @@ class Agent(EventEmitter):
         if host not in self.pools:
             self._add_pool(host, options)
         pool = self.pools[host]
-        if (self.cba_retry is not None or self.cba_hedge is not None) \
-                and isinstance(req, _TryRequest):
+        if isinstance(req, _TryRequest) and (
+                self.cba_retry is not None or self.cba_hedge is not None
+                or req.try_priority is not None):
             _TryTicket(self, pool, req)
         else:
             _RequestTicket(self, pool, req)
@@ -434,7 +447,8 @@ class Agent(EventEmitter):
                 path: str = "/", headers: Optional[Dict[str, str]] = None,
                 body: Optional[bytes] = None,
                 cb: Optional[Callable] = None,
-                retry: Any = None, hedge: Any = None) -> Any:
+                retry: Any = None, hedge: Any = None,
+                priority: Optional[int] = None) -> Any:
         """Convenience: run one request; cb(err, response) after the
         body has fully arrived.
 
@@ -449,11 +463,20 @@ class Agent(EventEmitter):
         returned when only ``hedge`` is on; ``hedge=False`` switches
         hedging off for this call, a mapping overrides keys of the
         agent's policy (all but ``budget``, ``window`` and
-        ``minSamples``)."""
+        ``minSamples``).
+
+        ``priority`` is the claim option of that name, for an agent
+        with ``claimQueue``: the class of the claim of every try and of
+        every hedge attempt of this request."""
         if isinstance(options_or_host, str):
             host = options_or_host
         else:
             host = options_or_host.get("host")
+        if priority is not None:
+            # checked here, against the agent's claimQueue, so that a
+            # bad value fails at the call and not in some later try
+            mod_utils.assert_claim_priority(priority, self.cba_queue,
+                                            "priority=", "an agent")
         if retry is not None or self.cba_retry is not None or \
                 hedge is not None or self.cba_hedge is not None:
             policy = self._retry_policy_for(retry)
@@ -461,9 +484,14 @@ class Agent(EventEmitter):
             if policy is not None or hpolicy is not None:
                 return self._request_driven(
                     policy, hpolicy, options_or_host, host, method, path,
-                    headers, body, cb)
-        req = HttpRequest(method, path, headers=headers, body=body,
-                          host=host)
+                    headers, body, cb, priority)
+        if priority is None:
+            req = HttpRequest(method, path, headers=headers, body=body,
+                              host=host)
+        else:
+            req = _TryRequest(method, path, headers=headers, body=body,
+                              host=host)
+            req.try_priority = priority
 
         if cb is not None:
             def on_resp(resp: HttpResponse) -> None:
@@ -482,7 +510,8 @@ class Agent(EventEmitter):
                             headers: Optional[Dict[str, str]] = None,
                             body: Optional[bytes] = None,
                             retry: Any = None,
-                            hedge: Any = None) -> HttpResponse:
+                            hedge: Any = None,
+                            priority: Optional[int] = None) -> HttpResponse:
         fut = self._loop.create_future()
 
         def cb(err: Optional[BaseException],
@@ -494,11 +523,11 @@ class Agent(EventEmitter):
             else:
                 fut.set_result(resp)
 
-        if retry is None and hedge is None:
+        if retry is None and hedge is None and priority is None:
             self.request(options_or_host, method, path, headers, body, cb)
         else:
             self.request(options_or_host, method, path, headers, body, cb,
-                         retry=retry, hedge=hedge)
+                         retry=retry, hedge=hedge, priority=priority)
         return await fut
 
     # -- retries --------------------------------------------------------------
@@ -556,10 +585,13 @@ class Agent(EventEmitter):
                         host: Any, method: str, path: str,
                         headers: Optional[Dict[str, str]],
                         body: Optional[bytes],
-                        cb: Optional[Callable]) -> Any:
+                        cb: Optional[Callable],
+                        priority: Optional[int] = None) -> Any:
         """One request under the retry driver (`policy`), the hedge
         driver (`hpolicy`), or both: then every try of the retry driver
-        is a hedged one."""
+        is a hedged one.  Both drivers start a try or an attempt through
+        start_real_try below, so that is where `priority` reaches every
+        claim of the request."""
         if not isinstance(host, str):
             if isinstance(options_or_host, Mapping):
                 host = options_or_host.get("hostname")
@@ -571,6 +603,8 @@ class Agent(EventEmitter):
                               host=host)
             if avoid:
                 req.try_avoid = avoid
+            if priority is not None:
+                req.try_priority = priority
             self.add_request(req, options_or_host)
             return req
 
@@ -796,6 +830,9 @@ class _TryRequest(HttpRequest):
 
     #: backend keys the try's claim is to avoid
     try_avoid: tuple = ()
+    #: the class of the try's claim (``priority=``), None for the
+    #: pool's default
+    try_priority: Optional[int] = None
     #: the try's claim handle and its slot, None until claimed
     try_handle: Any = None
     try_slot: Any = None
@@ -823,6 +860,8 @@ class _TryTicket(_RequestTicket):
         options: Dict[str, Any] = {"errorOnEmpty": agent.cba_err_on_empty}
         if req.try_avoid:
             options["avoidBackends"] = req.try_avoid
+        if req.try_priority is not None:
+            options["priority"] = req.try_priority
         self.waiter = pool.claim(options, self.claimed)
 
     def claimed(self, err: Optional[BaseException], connh: Any = None,

@@ -16,6 +16,7 @@ __all__ = [
     "NoBackendsError",
     "PoolFailedError",
     "PoolStoppingError",
+    "ClaimQueueFullError",
     "RequestTimeoutError",
     "ConnectionError_",
     "ConnectionTimeoutError",
@@ -107,6 +108,23 @@ class PoolStoppingError(CueballError):
         super().__init__(
             "Pool %s (%s) is stopping and cannot take new requests"
             % (uuid, getattr(pool, "p_domain", "?"))
+        )
+
+
+class ClaimQueueFullError(CueballError):
+    """A pool's ``claimQueue.maxQueued`` was reached and this claim was
+    the one to be served last.  ``displaced`` is False when the claim
+    was turned away on arrival, True when it had been waiting and a
+    later claim that is served ahead of it took its place."""
+
+    def __init__(self, pool: Any, displaced: bool = False) -> None:
+        self.pool = pool
+        self.displaced = displaced
+        uuid = str(getattr(pool, "p_uuid", "?")).split("-")[0]
+        super().__init__(
+            "Claim queue of pool %s (%s) is full; claim %s"
+            % (uuid, getattr(pool, "p_domain", "?"),
+               "displaced by a later claim" if displaced else "rejected")
         )
 
 

@@ -285,6 +285,18 @@ class ConnectionPool(FSM):
     p_lb_last: Optional[Dict[Any, Any]] = None
     _lb_gauges: Optional[tuple] = None
 
+    # Claim queue state, class-level like the rest: a pool without
+    # claimQueue has none of these in its instance dict, and its
+    # claim() is the class's.
+    #: the validated claimQueue option, defaults filled in
+    p_cq: Optional[Dict[str, Any]] = None
+    #: per class, the node of its last waiter as far as the pool knows
+    #: (it may have left the queue since); None with a single class
+    p_cq_last: Optional[List[Any]] = None
+    #: when the waiter queue last went from empty to non-empty, loop ms
+    p_cq_since = 0.0
+    _cq_gauge = None
+
     def __init__(self, options: Dict[str, Any]) -> None:
         if not callable(options.get("constructor")):
             raise TypeError("options.constructor (callable) is required")
@@ -474,6 +486,25 @@ class ConnectionPool(FSM):
                 except (AttributeError, ValueError):
                     pass
 
+        # Claim queue (opt-in): see the "claim queue" section below.
+        # Off means not one attribute is set here; on, claim() is
+        # replaced on this instance alone, claimBalancing or not.
+        cq = mod_utils.assert_claim_queue(options)
+        if cq is not None:
+            self.p_cq = cq
+            if cq["priorities"] > 1:
+                self.p_cq_last = [None] * cq["priorities"]
+            self.p_cq_since = 0.0
+            self.claim = self._claim_queued
+            if self._gauge is not None:
+                try:
+                    self._cq_gauge = self.p_collector.gauge(
+                        name="cueball_pool_queued_claims",
+                        help="Claims waiting in the pool's queue, by "
+                             "priority class")
+                except (AttributeError, ValueError):
+                    pass
+
         if options.get("resolver") is not None:
             self.p_resolver = options["resolver"]
             self.p_resolver_custom = True
@@ -616,6 +647,8 @@ class ConnectionPool(FSM):
             self._od_gauge.set(len(self.p_od_ejected), self._gauge_labels)
         if self._lb_gauges is not None:
             self._lb_publish()
+        if self._cq_gauge is not None:
+            self._cq_publish()
         if self.p_last_rebal_clamped:
             self.rebalance()
 
@@ -1716,41 +1749,12 @@ class ConnectionPool(FSM):
         """claim() of a pool with ``claimBalancing`` (installed on the
         instance): the same options, counters and return values; the
         handle is the runtime's own, its ticket a _BalancedClaimTicket."""
-        if callable(options) and cb is None:
-            cb = options
-            options = {}
-        options = options or {}
-        if cb is None:
-            raise TypeError("claim() requires a callback")
-        err_on_empty = bool(options.get("errorOnEmpty", False))
-        avoid = options.get("avoidBackends")
-        if avoid is not None:
-            avoid = self._assert_avoid(avoid)
-        if self.p_codel is not None:
-            if options.get("timeout") is not None:
-                raise ValueError("options.timeout not allowed when "
-                                 "targetClaimDelay has been set")
-            timeout = self.p_codel.get_max_idle()
-        elif options.get("timeout") is not None:
-            timeout = options["timeout"]
-        else:
-            timeout = math.inf
-
-        counters = self.p_counters
-        counters["claim"] = counters.get("claim", 0) + 1
-        st = self._fsm_state
-        if st == "stopping" or st == "stopped" or \
-                st == "stopping.backends":
-            return self._claim_shortcircuit(
-                cb, mod_errors.PoolStoppingError(self))
-        if st == "failed":
-            return self._claim_shortcircuit(
-                cb, mod_errors.PoolFailedError(self, self.p_last_error))
-        handle = ClaimHandle.fast(
-            self, mod_utils.maybe_capture_stack_trace(), cb,
-            self.p_claim_log, timeout, self._loop)
-        handle.on("stateChanged",
-                  _BalancedClaimTicket(self, handle, err_on_empty, avoid))
+        handle, stub, err_on_empty, avoid, _ = \
+            self._claim_begin(options, cb)
+        if handle is None:
+            return stub
+        handle.on("stateChanged", _BalancedClaimTicket(
+            self, handle, err_on_empty, avoid))
         return handle
 
     def _lb_publish(self) -> None:
@@ -1795,6 +1799,166 @@ class ConnectionPool(FSM):
         return {"enabled": True, "policy": lb["policy"],
                 "choices": lb["choices"], "decayTimeMs": lb["decayTime"],
                 "backends": out}
+
+    # -- claim queue (opt-in) ------------------------------------------------
+    #
+    # With ``claimQueue`` the waiter queue is bounded, has priority
+    # classes and may serve newest-first.  All of it is decided when a
+    # claim is linked: the head of p_waiters is always the next claim to
+    # serve, so whatever feeds a freed slot (the native dispatcher, the
+    # drains, CoDel) shifts the head as it always did.  The queue is
+    # kept sorted by class, class 0 at the head.
+
+    def _claim_queued(self, options: Any = None,
+                      cb: Optional[Callable] = None):
+        """claim() of a pool with ``claimQueue`` (installed on the
+        instance): the same options, counters and return values, and
+        ``priority``.  The handle is the runtime's own; its ticket is a
+        Python one on either runtime, so that every claim that has to
+        wait is placed by _ticket_slow."""
+        handle, stub, err_on_empty, avoid, prio = \
+            self._claim_begin(options, cb)
+        if handle is None:
+            return stub
+        handle.ch_priority = prio
+        if self.p_lb is not None:
+            ticket: Any = _BalancedClaimTicket(self, handle, err_on_empty,
+                                               avoid)
+        else:
+            ticket = _AvoidClaimTicket(self, handle, err_on_empty, avoid)
+        handle.on("stateChanged", ticket)
+        return handle
+
+    def _cq_newest_first(self, queued: int, now: float) -> bool:
+        """Would a claim that has to wait now be placed ahead of its
+        class?  `queued` is the length of the waiter queue."""
+        cq = self.p_cq
+        order = cq["order"]
+        if order == "fifo":
+            return False
+        if order == "lifo":
+            return True
+        # adaptive: a queue that has not been empty for lifoAfter ms is
+        # not draining, whatever was dequeued in between
+        return queued > 0 and now - self.p_cq_since >= cq["lifoAfter"]
+
+    def _cq_place(self, handle: ClaimHandle) -> bool:
+        """Link `handle` into the waiter queue where its class and the
+        queue's order put it, and enforce ``maxQueued``: the claim that
+        would be served last fails with ClaimQueueFullError, be it this
+        one (never linked; returns False) or the tail waiter.
+
+        Cost: O(1) with a single class (a push or an unshift, no walk).
+        With several classes O(priorities), from the remembered last
+        node of each class; when one of the remembered nodes has left
+        the queue (served, timed out, cancelled, shed), all of them are
+        recomputed in one for_each pass over the queue, at most once per
+        placement.
+
+        A claim that ``errorOnEmpty`` has just failed is not linked
+        either, nor counted as queued: a pool without the option pushes
+        such a handle as the reference does, a dead entry that the next
+        feed skips, but here it would take a live claim's place under
+        the bound."""
+        if not handle.is_in_state("waiting"):
+            return False
+        cq = self.p_cq
+        q = self.p_waiters
+        prio = handle.ch_priority
+        queued = q._len
+        now = self._loop.time() * 1000.0
+        if queued == 0:
+            # noted on arrival: displacing the only waiter below does
+            # not count as the queue having emptied
+            self.p_cq_since = now
+        newest_first = self._cq_newest_first(queued, now)
+
+        bound = cq["maxQueued"]
+        if bound is not None and queued >= bound:
+            tail = q.peek_last()
+            tail_prio = tail.ch_priority
+            if tail_prio < prio or (tail_prio == prio and not newest_first):
+                # this claim would be the tail
+                self._incr_counter("queue-rejected")
+                handle.fail(mod_errors.ClaimQueueFullError(self, False))
+                return False
+            self._incr_counter("queue-shed")
+            tail.fail(mod_errors.ClaimQueueFullError(self, True))
+
+        last = self.p_cq_last
+        if last is None:
+            node = q.unshift(handle) if newest_first else q.push(handle)
+        else:
+            # every class is looked at, not only the ones this placement
+            # needs: a node that has left the queue (the tail shed just
+            # now, for one) is let go of, and its handle with it
+            for n in last:
+                if n is not None and not n.linked:
+                    last = self._cq_remember()
+                    break
+            # behind the last waiter of the nearest class that is served
+            # ahead of this claim
+            anchor = None
+            for c in range(prio - 1 if newest_first else prio, -1, -1):
+                anchor = last[c]
+                if anchor is not None:
+                    break
+            if anchor is None:
+                node = q.unshift(handle)
+            else:
+                node = q.insert_after(anchor, handle)
+            if not newest_first or last[prio] is None:
+                last[prio] = node
+        handle.ch_waiter_node = node
+        if newest_first:
+            self._incr_counter("queue-lifo")
+        return True
+
+    def _cq_remember(self) -> List[Any]:
+        """Recompute the last node of every class in one pass."""
+        last: List[Any] = [None] * self.p_cq["priorities"]
+
+        def visit(hdl: ClaimHandle, node: Any) -> None:
+            last[hdl.ch_priority] = node
+
+        self.p_waiters.for_each(visit)
+        self.p_cq_last = last
+        return last
+
+    def _cq_census(self) -> List[int]:
+        counts = [0] * self.p_cq["priorities"]
+
+        def visit(hdl: ClaimHandle, node: Any) -> None:
+            counts[hdl.ch_priority] += 1
+
+        self.p_waiters.for_each(visit)
+        return counts
+
+    def _cq_publish(self) -> None:
+        for prio, n in enumerate(self._cq_census()):
+            self._cq_gauge.set(n, {**self._gauge_labels,
+                                   "priority": str(prio)})
+
+    def get_queue_stats(self) -> Dict[str, Any]:
+        """The claim queue as the pool sees it: ``{"enabled",
+        "maxQueued", "priorities", "order", "lifo", "queued",
+        "rejected", "shed", "lifoPlaced"}``.  ``lifo`` says whether a
+        claim that had to wait right now would be placed newest-first;
+        ``queued`` has one count per class, from a walk of the queue.
+        ``{"enabled": False}`` when the pool was created without
+        ``claimQueue``."""
+        cq = self.p_cq
+        if cq is None:
+            return {"enabled": False}
+        counters = self.p_counters
+        return {"enabled": True, "maxQueued": cq["maxQueued"],
+                "priorities": cq["priorities"], "order": cq["order"],
+                "lifo": self._cq_newest_first(
+                    self.p_waiters._len, self._loop.time() * 1000.0),
+                "queued": self._cq_census(),
+                "rejected": counters.get("queue-rejected", 0),
+                "shed": counters.get("queue-shed", 0),
+                "lifoPlaced": counters.get("queue-lifo", 0)}
 
     # -- slot lifecycle ----------------------------------------------------
     def add_connection(self, key: str) -> None:
@@ -2040,7 +2204,10 @@ class ConnectionPool(FSM):
         # entries linked until a dequeue walks past them,
         # lib/pool.js:934-951, which grows without bound when claims
         # time out faster than connections free up.)
-        handle.ch_waiter_node = self.p_waiters.push(handle)
+        if self.p_cq is None:
+            handle.ch_waiter_node = self.p_waiters.push(handle)
+        elif not self._cq_place(handle):
+            return
         self._note_demand()
         self._hwm_counter("max-claim-queue", self.p_waiters._len)
         self._incr_counter("queued-claim")
@@ -2056,6 +2223,8 @@ class ConnectionPool(FSM):
         ``avoidBackends``, an iterable of backend keys: among the idle
         slots the claim prefers one on another backend.  Only a
         preference: it never makes the claim wait, fail or time out.
+        On a pool with ``claimQueue`` also ``priority``, the claim's
+        class (an integer, 0 served first); a ValueError elsewhere.
         """
         # fast path: claim({}, cb) / claim(cb) with no CoDel — the
         # overwhelmingly common call shape on the hot path
@@ -2078,26 +2247,10 @@ class ConnectionPool(FSM):
             timeout = math.inf
             avoid = None
         else:
-            if callable(options) and cb is None:
-                cb = options
-                options = {}
-            options = options or {}
-            if cb is None:
-                raise TypeError("claim() requires a callback")
-            err_on_empty = bool(options.get("errorOnEmpty", False))
-            avoid = options.get("avoidBackends")
-            if avoid is not None:
-                avoid = self._assert_avoid(avoid)
-
-            if self.p_codel is not None:
-                if options.get("timeout") is not None:
-                    raise ValueError("options.timeout not allowed when "
-                                     "targetClaimDelay has been set")
-                timeout = self.p_codel.get_max_idle()
-            elif options.get("timeout") is not None:
-                timeout = options["timeout"]
-            else:
-                timeout = math.inf
+            # (a pool whose claim() this is has no claimQueue, so a
+            # ``priority`` has been refused in there)
+            cb, err_on_empty, avoid, _, timeout = \
+                self._claim_options(options, cb)
 
         counters = self.p_counters
         counters["claim"] = counters.get("claim", 0) + 1
@@ -2130,6 +2283,66 @@ class ConnectionPool(FSM):
                                   timeout, self._loop)
         handle.on("stateChanged", _ClaimTicket(self, handle, err_on_empty))
         return handle
+
+    def _claim_options(self, options: Any, cb: Optional[Callable]) -> tuple:
+        """Read and validate the arguments of a claim, for claim() and
+        for the claim()s that opted-in pools install on themselves:
+        ``(cb, err_on_empty, avoid, priority, timeout)``.  `priority` is
+        the claim's class on a pool with ``claimQueue`` (its default
+        when the claim names none) and None on any other, where naming
+        one is an error."""
+        if callable(options) and cb is None:
+            cb = options
+            options = {}
+        options = options or {}
+        if cb is None:
+            raise TypeError("claim() requires a callback")
+        err_on_empty = bool(options.get("errorOnEmpty", False))
+        avoid = options.get("avoidBackends")
+        if avoid is not None:
+            avoid = self._assert_avoid(avoid)
+        prio = options.get("priority")
+        if prio is not None:
+            prio = mod_utils.assert_claim_priority(prio, self.p_cq)
+        elif self.p_cq is not None:
+            prio = self.p_cq["defaultPriority"]
+
+        if self.p_codel is not None:
+            if options.get("timeout") is not None:
+                raise ValueError("options.timeout not allowed when "
+                                 "targetClaimDelay has been set")
+            timeout = self.p_codel.get_max_idle()
+        elif options.get("timeout") is not None:
+            timeout = options["timeout"]
+        else:
+            timeout = math.inf
+        return cb, err_on_empty, avoid, prio, timeout
+
+    def _claim_begin(self, options: Any, cb: Optional[Callable]) -> tuple:
+        """What the claim()s of opted-in pools share: the arguments, the
+        ``claim`` counter, the short-circuit of a pool that takes no
+        claims, and the runtime's handle.  Returns ``(handle, stub,
+        err_on_empty, avoid, priority)``: a handle that still needs its
+        ticket and None, or None and the cancel-only stub of the
+        short-circuit, which is then what claim() returns."""
+        cb, err_on_empty, avoid, prio, timeout = \
+            self._claim_options(options, cb)
+        counters = self.p_counters
+        counters["claim"] = counters.get("claim", 0) + 1
+        st = self._fsm_state
+        handle = stub = None
+        if st == "stopping" or st == "stopped" or \
+                st == "stopping.backends":
+            stub = self._claim_shortcircuit(
+                cb, mod_errors.PoolStoppingError(self))
+        elif st == "failed":
+            stub = self._claim_shortcircuit(
+                cb, mod_errors.PoolFailedError(self, self.p_last_error))
+        else:
+            handle = ClaimHandle.fast(
+                self, mod_utils.maybe_capture_stack_trace(), cb,
+                self.p_claim_log, timeout, self._loop)
+        return handle, stub, err_on_empty, avoid, prio
 
     def _assert_avoid(self, avoid: Any) -> Optional[frozenset]:
         """``avoidBackends``: an iterable of backend keys.  Returns the

@@ -41,12 +41,18 @@ class QueueNode:
         self._queue._len -= 1  # type: ignore[union-attr]
 
 
+#: the class above under a name that stays its own: the native core,
+#: when loaded, takes over ``QueueNode`` (end of the module), and the
+#: Queue below must go on building the nodes it can link
+_PyQueueNode = QueueNode
+
+
 class Queue:
     __slots__ = ("_head", "_tail", "_len")
 
     def __init__(self) -> None:
-        self._head = QueueNode(None, None)
-        self._tail = QueueNode(None, None)
+        self._head = _PyQueueNode(None, None)
+        self._tail = _PyQueueNode(None, None)
         self._head._next = self._tail
         self._tail._prev = self._head
         self._len = 0
@@ -62,7 +68,7 @@ class Queue:
 
     def push(self, value: Any) -> QueueNode:
         """Append; returns the node handle for later O(1) .remove()."""
-        n = QueueNode(self, value)
+        n = _PyQueueNode(self, value)
         prev = self._tail._prev
         n._prev = prev
         n._next = self._tail
@@ -70,6 +76,35 @@ class Queue:
         self._tail._prev = n
         self._len += 1
         return n
+
+    def unshift(self, value: Any) -> QueueNode:
+        """Link at the head; returns the node handle, as push() does."""
+        return self._link_after(self._head, value)
+
+    def insert_after(self, node: QueueNode, value: Any) -> QueueNode:
+        """Link directly behind `node`, which must be linked in this
+        queue (ValueError otherwise); returns the new node's handle."""
+        if type(node) is not _PyQueueNode or node._next is None or \
+                node._queue is not self:
+            raise ValueError("Queue.insert_after() needs a node linked "
+                             "in this queue")
+        return self._link_after(node, value)
+
+    def _link_after(self, prev: QueueNode, value: Any) -> QueueNode:
+        n = _PyQueueNode(self, value)
+        nxt = prev._next
+        n._prev = prev
+        n._next = nxt
+        prev._next = n
+        nxt._prev = n  # type: ignore[union-attr]
+        self._len += 1
+        return n
+
+    def peek_last(self) -> Any:
+        n = self._tail._prev
+        if n is self._head:
+            raise IndexError("peek_last from empty Queue")
+        return n.value  # type: ignore[union-attr]
 
     def shift(self) -> Any:
         n = self._head._next

@@ -332,7 +332,10 @@ class RetriedRequest(EventEmitter):
         elif isinstance(err, _CLAIM_FAILURES):
             reason = "claim-failure"
         else:
-            reason = None       # a stopping pool, a stopped agent
+            # a stopping pool, a stopped agent, or a full claim queue
+            # (ClaimQueueFullError): the pool has just said that it is
+            # overloaded, so no retry and nothing off the budget
+            reason = None
         self._try_failed(reason, None, err)
 
     def _on_try_timeout(self) -> None:

@@ -373,6 +373,103 @@ def assert_claim_balancing(options: Mapping[str, Any]
             "rng": rng}
 
 
+_QUEUE_KEYS = ("maxQueued", "priorities", "defaultPriority", "order",
+               "lifoAfter")
+_QUEUE_ORDERS = ("fifo", "lifo", "adaptive")
+#: the most classes a claim queue may have
+MAX_CLAIM_PRIORITIES = 8
+
+
+def assert_claim_queue(options: Mapping[str, Any]
+                       ) -> Optional[Dict[str, Any]]:
+    """Validate ``claimQueue`` and return it with every default filled
+    in, or None when the option is off.  ``lifoAfter`` is None under the
+    orders that do not use it; under ``"adaptive"`` its default is the
+    pool's ``targetClaimDelay``."""
+    cq = options.get("claimQueue")
+    if cq is None:
+        return None
+    name = "options.claimQueue"
+    if not isinstance(cq, Mapping):
+        raise TypeError("%s must be a mapping" % name)
+    extra = set(cq.keys()) - set(_QUEUE_KEYS)
+    if extra:
+        raise ValueError("%s has unknown keys: %r"
+                         % (name, sorted(extra, key=str)))
+
+    bound = cq.get("maxQueued")
+    if bound is not None:
+        if not isinstance(bound, int) or isinstance(bound, bool):
+            raise TypeError("%s.maxQueued must be an int or None" % name)
+        if bound < 1:
+            raise ValueError("%s.maxQueued must be >= 1" % name)
+
+    classes = cq.get("priorities")
+    if classes is None:
+        classes = 1
+    if not isinstance(classes, int) or isinstance(classes, bool):
+        raise TypeError("%s.priorities must be an int" % name)
+    if not (1 <= classes <= MAX_CLAIM_PRIORITIES):
+        raise ValueError("%s.priorities must be in 1..%d"
+                         % (name, MAX_CLAIM_PRIORITIES))
+
+    default = cq.get("defaultPriority")
+    if default is None:
+        default = 0
+    if not isinstance(default, int) or isinstance(default, bool):
+        raise TypeError("%s.defaultPriority must be an int" % name)
+    if not (0 <= default < classes):
+        raise ValueError("%s.defaultPriority must be in 0..%d"
+                         % (name, classes - 1))
+
+    order = cq.get("order")
+    if order is None:
+        order = "fifo"
+    if not isinstance(order, str):
+        raise TypeError("%s.order must be a string" % name)
+    if order not in _QUEUE_ORDERS:
+        raise ValueError("%s.order must be one of %r"
+                         % (name, list(_QUEUE_ORDERS)))
+
+    after = cq.get("lifoAfter")
+    if after is not None:
+        if not _num(after):
+            raise TypeError("%s.lifoAfter must be a number" % name)
+        if order != "adaptive":
+            raise ValueError('%s.lifoAfter needs order "adaptive"' % name)
+        if not math.isfinite(after) or after < 0:
+            raise ValueError("%s.lifoAfter must be finite and >= 0" % name)
+    elif order == "adaptive":
+        after = options.get("targetClaimDelay")
+        if after is None:
+            raise ValueError('%s.lifoAfter is required under order '
+                             '"adaptive" unless the pool has '
+                             'targetClaimDelay' % name)
+        assert_claim_delay(after)
+
+    return {"maxQueued": bound, "priorities": classes,
+            "defaultPriority": default, "order": order,
+            "lifoAfter": after}
+
+
+def assert_claim_priority(priority: Any, cq: Optional[Mapping[str, Any]],
+                          name: str = "options.priority",
+                          owner: str = "a pool") -> int:
+    """Validate a claim's class against `cq`, the validated
+    ``claimQueue`` of the pool or agent asked (None when it has none):
+    an int that is not a bool, in ``0 .. priorities-1``.  Naming a class
+    where there is no ``claimQueue`` is a ValueError."""
+    if not isinstance(priority, int) or isinstance(priority, bool):
+        raise TypeError("%s must be an int" % name)
+    if cq is None:
+        raise ValueError("%s needs %s that was created with "
+                         "options.claimQueue" % (name, owner))
+    if not (0 <= priority < cq["priorities"]):
+        raise ValueError("%s must be in 0..%d"
+                         % (name, cq["priorities"] - 1))
+    return priority
+
+
 RETRY_REASONS =("reset", "timeout", "status", "claim-failure")
 
 _RETRY_KEYS = ("maxRetries", "retryOn", "retryStatuses", "methods",
