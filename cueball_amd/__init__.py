@@ -8,6 +8,7 @@ shedding and rich introspection.  Built on asyncio with its own Moore
 FSM runtime and DNS protocol engine.
 """
 
+from .affinity import order as affinity_order
 from .codel import ControlledDelay
 from .connection import TcpConnection, tcp_constructor
 from .connection_fsm import ClaimHandle, ConnectionSlotFSM
@@ -43,6 +44,7 @@ __all__ = [
     "config_for_ip_or_domain",
     "parse_ip_or_domain",
     "srv_key",
+    "affinity_order",
     "ClaimHandle",
     "ConnectionSlotFSM",
     "ControlledDelay",

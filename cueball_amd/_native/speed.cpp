@@ -6954,7 +6954,112 @@ speed_set_tracer(PyObject *mod, PyObject *fn)
     Py_RETURN_NONE;
 }
 
+/* ------------------------------------------------------------------ */
+/* Key affinity (cueball_amd/affinity.py holds the definition and the  */
+/* Python twins): what a keyed claim computes on every try.            */
+
+static inline uint64_t
+aff_fnv1a64(const unsigned char *p, Py_ssize_t n)
+{
+    uint64_t h = 0xcbf29ce484222325ULL;
+    for (Py_ssize_t i = 0; i < n; i++)
+        h = (h ^ p[i]) * 0x100000001b3ULL;
+    return h;
+}
+
+static inline uint64_t
+aff_mix64(uint64_t z)
+{
+    z ^= z >> 30;
+    z *= 0xbf58476d1ce4e5b9ULL;
+    z ^= z >> 27;
+    z *= 0x94d049bb133111ebULL;
+    z ^= z >> 31;
+    return z;
+}
+
+/* affinity_hash(bytes) -> int: FNV-1a, 64 bits */
+static PyObject *
+speed_affinity_hash(PyObject *mod, PyObject *data)
+{
+    (void)mod;
+    if (!PyBytes_Check(data)) {
+        PyErr_SetString(PyExc_TypeError, "affinity_hash: bytes required");
+        return NULL;
+    }
+    return PyLong_FromUnsignedLongLong(aff_fnv1a64(
+        (const unsigned char *)PyBytes_AS_STRING(data),
+        PyBytes_GET_SIZE(data)));
+}
+
+/* affinity_rank(bytes, tuple of backend hashes) -> tuple of indices by
+ * descending score, best first; equal scores keep their input order */
+static PyObject *
+speed_affinity_rank(PyObject *mod, PyObject *const *args, Py_ssize_t nargs)
+{
+    (void)mod;
+    if (nargs != 2 || !PyBytes_Check(args[0]) || !PyTuple_Check(args[1])) {
+        PyErr_SetString(PyExc_TypeError,
+            "affinity_rank: bytes and a tuple of backend hashes required");
+        return NULL;
+    }
+    uint64_t kh = aff_fnv1a64(
+        (const unsigned char *)PyBytes_AS_STRING(args[0]),
+        PyBytes_GET_SIZE(args[0]));
+    Py_ssize_t n = PyTuple_GET_SIZE(args[1]);
+    uint64_t sbuf[32];
+    Py_ssize_t ibuf[32];
+    uint64_t *sc = sbuf;
+    Py_ssize_t *ix = ibuf;
+    if (n > 32) {
+        sc = (uint64_t *)PyMem_Malloc((size_t)n * sizeof(uint64_t));
+        ix = (Py_ssize_t *)PyMem_Malloc((size_t)n * sizeof(Py_ssize_t));
+        if (sc == NULL || ix == NULL) {
+            PyMem_Free(sc);
+            PyMem_Free(ix);
+            return PyErr_NoMemory();
+        }
+    }
+    PyObject *out = NULL;
+    Py_ssize_t i;
+    for (i = 0; i < n; i++) {
+        uint64_t h = PyLong_AsUnsignedLongLong(PyTuple_GET_ITEM(args[1], i));
+        if (h == (uint64_t)-1 && PyErr_Occurred())
+            goto done;
+        /* a stable insertion sort: the backends of a pool are few */
+        uint64_t s = aff_mix64(kh ^ h);
+        Py_ssize_t j = i;
+        while (j > 0 && sc[j - 1] < s) {
+            sc[j] = sc[j - 1];
+            ix[j] = ix[j - 1];
+            j--;
+        }
+        sc[j] = s;
+        ix[j] = i;
+    }
+    out = PyTuple_New(n);
+    if (out == NULL)
+        goto done;
+    for (i = 0; i < n; i++) {
+        PyObject *v = PyLong_FromSsize_t(ix[i]);
+        if (v == NULL) {
+            Py_CLEAR(out);
+            goto done;
+        }
+        PyTuple_SET_ITEM(out, i, v);
+    }
+done:
+    if (sc != sbuf) {
+        PyMem_Free(sc);
+        PyMem_Free(ix);
+    }
+    return out;
+}
+
 PyMethodDef speed_methods[] = {
+    {"affinity_hash", speed_affinity_hash, METH_O, NULL},
+    {"affinity_rank", (PyCFunction)(void (*)(void))speed_affinity_rank,
+     METH_FASTCALL, NULL},
     {"_set_claim_helpers",
      (PyCFunction)(void (*)(void))speed_set_claim_helpers, METH_FASTCALL,
      NULL},

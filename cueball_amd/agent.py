@@ -85,6 +85,8 @@ class Agent(EventEmitter):
     cba_balancing: Optional[Dict[str, Any]] = None
     #: the validated ``claimQueue`` option, likewise
     cba_queue: Optional[Dict[str, Any]] = None
+    #: the validated ``claimAffinity`` option, likewise
+    cba_affinity: Optional[Dict[str, Any]] = None
 
     def __init__(self, options: Dict[str, Any]) -> None:
         super().__init__()
@@ -170,6 +172,10 @@ class Agent(EventEmitter):
         queue = mod_utils.assert_claim_queue(options)
         if queue is not None:
             self.cba_queue = queue
+        # Key affinity (opt-in), likewise.
+        affinity = mod_utils.assert_claim_affinity(options)
+        if affinity is not None:
+            self.cba_affinity = affinity
 
         for host in options.get("initialDomains") or ():
             self._add_pool(host, {})
@@ -281,6 +287,9 @@ class Agent(EventEmitter):
             pool_opts["claimBalancing"] = dict(self.cba_balancing)
         if self.cba_queue is not None:
             pool_opts["claimQueue"] = dict(self.cba_queue)
+        if self.cba_affinity is not None:
+            pool_opts["claimAffinity"] = {
+                "loadFactor": self.cba_affinity["loadFactor"]}
         if self.cba_ping is not None:
             pool_opts["checkTimeout"] = self.cba_ping_interval or 30000
             pool_opts["checker"] = \
@@ -325,6 +334,10 @@ class Agent(EventEmitter):
     def get_queue_stats(self, host: str) -> Dict[str, Any]:
         """``ConnectionPool.get_queue_stats()`` of `host`'s pool."""
         return self._pool_for(host).get_queue_stats()
+
+    def get_affinity_stats(self, host: str) -> Dict[str, Any]:
+        """``ConnectionPool.get_affinity_stats()`` of `host`'s pool."""
+        return self._pool_for(host).get_affinity_stats()
 
     def _pool_for(self, host: str) -> ConnectionPool:
         pool = self.pools.get(host)
@@ -438,7 +451,8 @@ class Agent(EventEmitter):
         pool = self.pools[host]
         if isinstance(req, _TryRequest) and (
                 self.cba_retry is not None or self.cba_hedge is not None
-                or req.try_priority is not None):
+                or req.try_priority is not None
+                or req.try_affinity is not None):
             _TryTicket(self, pool, req)
         else:
             _RequestTicket(self, pool, req)
@@ -448,7 +462,8 @@ class Agent(EventEmitter):
                 body: Optional[bytes] = None,
                 cb: Optional[Callable] = None,
                 retry: Any = None, hedge: Any = None,
-                priority: Optional[int] = None) -> Any:
+                priority: Optional[int] = None,
+                affinityKey: Any = None) -> Any:
         """Convenience: run one request; cb(err, response) after the
         body has fully arrived.
 
@@ -467,7 +482,13 @@ class Agent(EventEmitter):
 
         ``priority`` is the claim option of that name, for an agent
         with ``claimQueue``: the class of the claim of every try and of
-        every hedge attempt of this request."""
+        every hedge attempt of this request.
+
+        ``affinityKey`` (bytes or str) is the claim option of that
+        name, for an agent with ``claimAffinity``: every try and every
+        hedge attempt of this request prefers the backends in the key's
+        order.  A retry or a hedge attempt avoids the backends tried
+        before it, and so lands on the key's next choice."""
         if isinstance(options_or_host, str):
             host = options_or_host
         else:
@@ -477,6 +498,9 @@ class Agent(EventEmitter):
             # bad value fails at the call and not in some later try
             mod_utils.assert_claim_priority(priority, self.cba_queue,
                                             "priority=", "an agent")
+        if affinityKey is not None:
+            affinityKey = mod_utils.assert_affinity_key(
+                affinityKey, self.cba_affinity, "affinityKey=", "an agent")
         if retry is not None or self.cba_retry is not None or \
                 hedge is not None or self.cba_hedge is not None:
             policy = self._retry_policy_for(retry)
@@ -484,14 +508,15 @@ class Agent(EventEmitter):
             if policy is not None or hpolicy is not None:
                 return self._request_driven(
                     policy, hpolicy, options_or_host, host, method, path,
-                    headers, body, cb, priority)
-        if priority is None:
+                    headers, body, cb, priority, affinityKey)
+        if priority is None and affinityKey is None:
             req = HttpRequest(method, path, headers=headers, body=body,
                               host=host)
         else:
             req = _TryRequest(method, path, headers=headers, body=body,
                               host=host)
             req.try_priority = priority
+            req.try_affinity = affinityKey
 
         if cb is not None:
             def on_resp(resp: HttpResponse) -> None:
@@ -511,7 +536,8 @@ class Agent(EventEmitter):
                             body: Optional[bytes] = None,
                             retry: Any = None,
                             hedge: Any = None,
-                            priority: Optional[int] = None) -> HttpResponse:
+                            priority: Optional[int] = None,
+                            affinityKey: Any = None) -> HttpResponse:
         fut = self._loop.create_future()
 
         def cb(err: Optional[BaseException],
@@ -523,11 +549,13 @@ class Agent(EventEmitter):
             else:
                 fut.set_result(resp)
 
-        if retry is None and hedge is None and priority is None:
+        if retry is None and hedge is None and priority is None and \
+                affinityKey is None:
             self.request(options_or_host, method, path, headers, body, cb)
         else:
             self.request(options_or_host, method, path, headers, body, cb,
-                         retry=retry, hedge=hedge, priority=priority)
+                         retry=retry, hedge=hedge, priority=priority,
+                         affinityKey=affinityKey)
         return await fut
 
     # -- retries --------------------------------------------------------------
@@ -586,12 +614,14 @@ class Agent(EventEmitter):
                         headers: Optional[Dict[str, str]],
                         body: Optional[bytes],
                         cb: Optional[Callable],
-                        priority: Optional[int] = None) -> Any:
+                        priority: Optional[int] = None,
+                        affinity: Optional[bytes] = None) -> Any:
         """One request under the retry driver (`policy`), the hedge
         driver (`hpolicy`), or both: then every try of the retry driver
         is a hedged one.  Both drivers start a try or an attempt through
-        start_real_try below, so that is where `priority` reaches every
-        claim of the request."""
+        start_real_try below, so that is where `priority` and
+        `affinity` (the bytes of ``affinityKey=``) reach every claim of
+        the request."""
         if not isinstance(host, str):
             if isinstance(options_or_host, Mapping):
                 host = options_or_host.get("hostname")
@@ -605,6 +635,8 @@ class Agent(EventEmitter):
                 req.try_avoid = avoid
             if priority is not None:
                 req.try_priority = priority
+            if affinity is not None:
+                req.try_affinity = affinity
             self.add_request(req, options_or_host)
             return req
 
@@ -833,6 +865,8 @@ class _TryRequest(HttpRequest):
     #: the class of the try's claim (``priority=``), None for the
     #: pool's default
     try_priority: Optional[int] = None
+    #: the affinity key of the try's claim (``affinityKey=``), as bytes
+    try_affinity: Optional[bytes] = None
     #: the try's claim handle and its slot, None until claimed
     try_handle: Any = None
     try_slot: Any = None
@@ -862,6 +896,8 @@ class _TryTicket(_RequestTicket):
             options["avoidBackends"] = req.try_avoid
         if req.try_priority is not None:
             options["priority"] = req.try_priority
+        if req.try_affinity is not None:
+            options["affinityKey"] = req.try_affinity
         self.waiter = pool.claim(options, self.claimed)
 
     def claimed(self, err: Optional[BaseException], connh: Any = None,

@@ -23,6 +23,7 @@ import time as mod_time
 import uuid as mod_uuid
 from typing import Any, Callable, Dict, List, Mapping, Optional
 
+from . import affinity as mod_affinity
 from . import balance as mod_balance
 from . import codel as mod_codel
 from . import errors as mod_errors
@@ -168,6 +169,40 @@ class _BalancedClaimTicket:
             handle.remove_listener("stateChanged", self)
 
 
+class _AffinityClaimTicket:
+    """The ticket of a claim that carries ``affinityKey``, on a pool with
+    ``claimAffinity``: the Python path, on either runtime, with the key's
+    rendezvous order choosing among the idle slots
+    (``pool._ticket_affine``).  ``counted`` is set once the claim's
+    outcome has been counted: a claim is counted once, however often it
+    returns to 'waiting'."""
+
+    __slots__ = ("pool", "handle", "err_on_empty", "avoid", "key",
+                 "counted")
+
+    _cueball_ticket = True
+
+    def __init__(self, pool: "ConnectionPool", handle: ClaimHandle,
+                 err_on_empty: bool, avoid: Optional[frozenset],
+                 key: bytes) -> None:
+        self.pool = pool
+        self.handle = handle
+        self.err_on_empty = err_on_empty
+        self.avoid = avoid
+        self.key = key
+        self.counted = False
+
+    def __call__(self, st: str) -> None:
+        handle = self.handle
+        if handle is None:
+            return
+        if st == "waiting":
+            self.pool._ticket_affine(handle, self)
+        elif st in ("released", "closed", "cancelled", "failed"):
+            self.handle = None
+            handle.remove_listener("stateChanged", self)
+
+
 _NativeClaimTicket = None
 _native_claim_fast = None
 _native_pool_claim = None
@@ -296,6 +331,22 @@ class ConnectionPool(FSM):
     #: when the waiter queue last went from empty to non-empty, loop ms
     p_cq_since = 0.0
     _cq_gauge = None
+
+    # Key affinity state, class-level like the rest: a pool without
+    # claimAffinity has none of these in its instance dict, and its
+    # claim() is the class's.
+    #: the validated claimAffinity option, defaults filled in
+    p_af: Optional[Dict[str, Any]] = None
+    #: key -> affinity.backend_hash(key), for the backends the resolver
+    #: lists: set when one is added, dropped when it is removed
+    p_af_hashes: Optional[Dict[str, int]] = None
+    #: (backend keys sorted, their hashes in that order), what
+    #: affinity.rank reads; None after the resolver changed the set
+    p_af_ranked: Optional[tuple] = None
+    #: key -> [keyed claims that had it as first choice, keyed claims
+    #: placed on it]
+    p_af_placed: Optional[Dict[str, List[int]]] = None
+    _af_gauge = None
 
     def __init__(self, options: Dict[str, Any]) -> None:
         if not callable(options.get("constructor")):
@@ -505,6 +556,26 @@ class ConnectionPool(FSM):
                 except (AttributeError, ValueError):
                     pass
 
+        # Key affinity (opt-in): see the "key affinity" section below.
+        # Off means not one attribute is set here.  On, claim() is
+        # replaced on this instance alone, unless claimBalancing or
+        # claimQueue has done so: their claim()s know about keys.
+        af = mod_utils.assert_claim_affinity(options)
+        if af is not None:
+            self.p_af = af
+            self.p_af_hashes = {}
+            self.p_af_placed = {}
+            if lb is None and cq is None:
+                self.claim = self._claim_affine
+            if self._gauge is not None:
+                try:
+                    self._af_gauge = self.p_collector.gauge(
+                        name="cueball_pool_affinity_hit_ratio",
+                        help="Share of the claims with an affinityKey "
+                             "that got the key's first choice")
+                except (AttributeError, ValueError):
+                    pass
+
         if options.get("resolver") is not None:
             self.p_resolver = options["resolver"]
             self.p_resolver_custom = True
@@ -649,6 +720,8 @@ class ConnectionPool(FSM):
             self._lb_publish()
         if self._cq_gauge is not None:
             self._cq_publish()
+        if self._af_gauge is not None:
+            self._af_publish()
         if self.p_last_rebal_clamped:
             self.rebalance()
 
@@ -662,6 +735,9 @@ class ConnectionPool(FSM):
             self.p_ranks[k] = (backend.get("priority", 0),
                                backend.get("weight", 0))
             self.p_rank_gen += 1
+        if self.p_af_hashes is not None:
+            self.p_af_hashes[k] = mod_affinity.backend_hash(k)
+            self.p_af_ranked = None
         self.rebalance()
 
     def _on_resolver_changed(self, k: str, backend: Dict[str, Any]) -> None:
@@ -704,6 +780,10 @@ class ConnectionPool(FSM):
         if self.p_lb_backends is not None:
             # likewise; leases still open keep the record they began on
             self.p_lb_backends.pop(k, None)
+        if self.p_af_hashes is not None:
+            self.p_af_hashes.pop(k, None)
+            self.p_af_placed.pop(k, None)
+            self.p_af_ranked = None
         # Slots unlink themselves (and rebalance) from the stateChanged
         # handler in add_connection once they stop; here we only flag
         # them unwanted (lib/pool.js:300-313).
@@ -880,6 +960,9 @@ class ConnectionPool(FSM):
         self.p_keys = []
         self.p_connections = {}
         self.p_backends = {}
+        if self.p_af_hashes is not None:
+            self.p_af_hashes = {}
+            self.p_af_ranked = None
         self.p_rebal_timer.cancel()
         self.p_shuffle_timer.cancel()
         self.p_lp_timer.cancel()
@@ -1749,12 +1832,16 @@ class ConnectionPool(FSM):
         """claim() of a pool with ``claimBalancing`` (installed on the
         instance): the same options, counters and return values; the
         handle is the runtime's own, its ticket a _BalancedClaimTicket."""
-        handle, stub, err_on_empty, avoid, _ = \
+        handle, stub, err_on_empty, avoid, _, akey = \
             self._claim_begin(options, cb)
         if handle is None:
             return stub
-        handle.on("stateChanged", _BalancedClaimTicket(
-            self, handle, err_on_empty, avoid))
+        if akey is not None:
+            ticket: Any = _AffinityClaimTicket(self, handle, err_on_empty,
+                                               avoid, akey)
+        else:
+            ticket = _BalancedClaimTicket(self, handle, err_on_empty, avoid)
+        handle.on("stateChanged", ticket)
         return handle
 
     def _lb_publish(self) -> None:
@@ -1816,14 +1903,17 @@ class ConnectionPool(FSM):
         ``priority``.  The handle is the runtime's own; its ticket is a
         Python one on either runtime, so that every claim that has to
         wait is placed by _ticket_slow."""
-        handle, stub, err_on_empty, avoid, prio = \
+        handle, stub, err_on_empty, avoid, prio, akey = \
             self._claim_begin(options, cb)
         if handle is None:
             return stub
         handle.ch_priority = prio
-        if self.p_lb is not None:
-            ticket: Any = _BalancedClaimTicket(self, handle, err_on_empty,
-                                               avoid)
+        if akey is not None:
+            ticket: Any = _AffinityClaimTicket(self, handle, err_on_empty,
+                                               avoid, akey)
+        elif self.p_lb is not None:
+            ticket = _BalancedClaimTicket(self, handle, err_on_empty,
+                                          avoid)
         else:
             ticket = _AvoidClaimTicket(self, handle, err_on_empty, avoid)
         handle.on("stateChanged", ticket)
@@ -1959,6 +2049,268 @@ class ConnectionPool(FSM):
                 "rejected": counters.get("queue-rejected", 0),
                 "shed": counters.get("queue-shed", 0),
                 "lifoPlaced": counters.get("queue-lifo", 0)}
+
+    # -- key affinity (opt-in) -----------------------------------------------
+    #
+    # With ``claimAffinity`` a claim may carry an ``affinityKey``, and
+    # among the idle connections it then prefers the backend that
+    # rendezvous hashing ranks first for the key (cueball_amd.affinity),
+    # so that the same key keeps reaching the same backend from every
+    # client that sees the same DNS.  A soft preference, like
+    # avoidBackends: decided when the claim's ticket runs, among what is
+    # idle then.  A claim that finds nothing idle waits like any other,
+    # and is fed by whatever frees up first.
+    #
+    # The load bound reads the slots themselves: a slot is in use from
+    # the try_ that hands it over (its state changes there and then, so
+    # a burst of claims in one loop turn sees its own picks) until the
+    # slot has heard of the lease's end.  Nothing is kept per lease.
+
+    def _af_order(self, key: bytes) -> List[str]:
+        """Every backend the resolver lists, in the order `key` prefers
+        them."""
+        ranked = self.p_af_ranked
+        if ranked is None:
+            hashes = self.p_af_hashes
+            keys = tuple(sorted(hashes))
+            ranked = self.p_af_ranked = (
+                keys, tuple(hashes[k] for k in keys))
+        keys, hashes = ranked
+        return [keys[i] for i in mod_affinity.rank(key, hashes)]
+
+    def _af_census(self) -> tuple:
+        """``({key: connections in use}, their sum, backends with a
+        connection that is idle or in use)``.  A pinger's lease is
+        neither."""
+        in_use: Dict[str, int] = {}
+        total = 0
+        live = 0
+        for k, conns in self.p_connections.items():
+            n = 0
+            idle = False
+            for fsm in conns:
+                st = fsm._fsm_state
+                if st == "idle":
+                    idle = True
+                elif st == "busy":
+                    hdl = fsm.csf_handle
+                    if hdl is not None and not hdl.ch_pinger:
+                        n += 1
+            if n > 0 or idle:
+                live += 1
+            in_use[k] = n
+            total += n
+        return in_use, total, live
+
+    def _af_unused(self, key: str) -> bool:
+        """Has backend `key` no connection in use?  Such a backend is
+        under any bound, the cap being 1 at the least, so the common
+        case needs no census."""
+        for fsm in self.p_connections.get(key, ()):
+            if fsm._fsm_state == "busy":
+                hdl = fsm.csf_handle
+                if hdl is not None and not hdl.ch_pinger:
+                    return False
+        return True
+
+    def _af_pick(self, order: List[str]) -> Optional[tuple]:
+        """Unlink the idle slot that `order` (the key's, avoided
+        backends moved to its end) chooses, and return it with whether
+        the first backend of the order had an idle slot; None when
+        nothing is idle.  One walk, with the queue discipline of
+        _idle_avoiding: stale entries that are met are unlinked, idle
+        slots that are passed over stay linked where they are.  The walk
+        ends at the first choice's first idle slot when that settles
+        it, which it does unless the load bound has a say."""
+        entries = list(self.p_idleq)
+        first = order[0] if order else None
+        firsts: Dict[Any, ConnectionSlotFSM] = {}
+        fraction = self.p_af["loadFraction"]
+        picked = None
+        at = 0
+        for fsm in entries:
+            at += 1
+            if fsm._fsm_state != "idle":
+                fsm.p_idleq_node.remove()
+                fsm.p_idleq_node = None
+                continue
+            k = fsm.csf_backend.get("key")
+            if k not in firsts:
+                firsts[k] = fsm
+                if k == first:
+                    if fraction is None or self._af_unused(k):
+                        picked = fsm
+                    break
+        if picked is None:
+            for fsm in entries[at:]:
+                if fsm._fsm_state != "idle":
+                    fsm.p_idleq_node.remove()
+                    fsm.p_idleq_node = None
+                    continue
+                k = fsm.csf_backend.get("key")
+                if k not in firsts:
+                    firsts[k] = fsm
+            if not firsts:
+                return None
+            cap = None
+            in_use: Dict[str, int] = {}
+            if fraction is not None:
+                in_use, total, live = self._af_census()
+                cap = mod_affinity.cap_of(fraction[0], fraction[1],
+                                          total, live or 1)
+            spill = None
+            for k in order:
+                fsm = firsts.get(k)
+                if fsm is None:
+                    continue
+                if cap is None or in_use.get(k, 0) < cap:
+                    picked = fsm
+                    break
+                if spill is None:
+                    spill = fsm
+            if picked is None:
+                # every backend with an idle slot is over the bound (or,
+                # the slot of a backend that is gone already: the head
+                # of the queue)
+                picked = spill if spill is not None else \
+                    next(iter(firsts.values()))
+        picked.p_idleq_node.remove()
+        picked.p_idleq_node = None
+        return picked, first in firsts
+
+    def _af_count(self, ticket: _AffinityClaimTicket, outcome: str,
+                  first: Optional[str], placed: Optional[str]) -> None:
+        ticket.counted = True
+        counters = self.p_counters
+        counters["affinity-claim"] = counters.get("affinity-claim", 0) + 1
+        counters[outcome] = counters.get(outcome, 0) + 1
+        books = self.p_af_placed
+        for i, k in ((0, first), (1, placed)):
+            if k is not None and k in self.p_backends:
+                ent = books.get(k)
+                if ent is None:
+                    ent = books[k] = [0, 0]
+                ent[i] += 1
+
+    def _ticket_affine(self, handle: ClaimHandle,
+                       ticket: _AffinityClaimTicket) -> None:
+        """_ticket_slow with the key's choice in place of the head of
+        the idle queue; everything else is _ticket_slow itself."""
+        order: List[str] = []
+        if handle.is_in_state("waiting") and \
+                self._fsm_state in ("starting", "running"):
+            order = self._af_order(ticket.key)
+            avoid = ticket.avoid
+            if avoid is not None:
+                order = [k for k in order if k not in avoid] + \
+                    [k for k in order if k in avoid]
+            found = self._af_pick(order)
+            if found is not None:
+                fsm, first_idle = found
+                key = fsm.csf_backend.get("key")
+                rec = None
+                if self.p_lb is not None:
+                    # the balancer's books count the claim as one of
+                    # their own (see _ticket_balanced)
+                    rec = self._lb_record(key)
+                    rec.outstanding += 1
+                handle.try_(fsm)
+                if handle._fsm_state in ("waiting", "cancelled"):
+                    # rejected: the slot's socket was gone already.  The
+                    # handle's 'waiting' brings the ticket back here.
+                    if rec is not None:
+                        rec.outstanding -= 1
+                else:
+                    if rec is not None:
+                        self.p_lb_handed[fsm] = (handle, rec)
+                    if not ticket.counted:
+                        first = order[0] if order else None
+                        if key == first:
+                            outcome = "affinity-hit"
+                        elif first_idle:
+                            outcome = "affinity-spill-load"
+                        else:
+                            outcome = "affinity-spill-busy"
+                        self._af_count(ticket, outcome, first, key)
+                self._note_demand()
+                return
+        # nothing idle (the walk has emptied the queue), or the pool is
+        # on its way out
+        self._ticket_slow(handle, ticket.err_on_empty)
+        if not ticket.counted and handle._fsm_state == "waiting":
+            self._af_count(ticket, "affinity-queued",
+                           order[0] if order else None, None)
+
+    def _claim_affine(self, options: Any = None,
+                      cb: Optional[Callable] = None):
+        """claim() of a pool with ``claimAffinity`` and neither
+        ``claimBalancing`` nor ``claimQueue`` (installed on the
+        instance).  A claim without a key is the class's claim(), native
+        fast path and all; one with a key gets the runtime's own handle
+        and an _AffinityClaimTicket."""
+        if not isinstance(options, Mapping) or \
+                options.get("affinityKey") is None:
+            return ConnectionPool.claim(self, options, cb)
+        handle, stub, err_on_empty, avoid, _, akey = \
+            self._claim_begin(options, cb)
+        if handle is None:
+            return stub
+        handle.on("stateChanged", _AffinityClaimTicket(
+            self, handle, err_on_empty, avoid, akey))
+        return handle
+
+    def _af_publish(self) -> None:
+        counters = self.p_counters
+        claims = counters.get("affinity-claim", 0)
+        if claims > 0:
+            self._af_gauge.set(counters.get("affinity-hit", 0) / claims,
+                               self._gauge_labels)
+
+    def get_affinity_order(self, key: Any) -> List[str]:
+        """The keys of the backends the resolver lists right now, in
+        the order a claim with ``affinityKey`` `key` (bytes, or a str,
+        read as UTF-8) prefers them: a function of the key and of DNS
+        alone, the same in every client.  A ValueError on a pool
+        without ``claimAffinity``."""
+        return self._af_order(mod_utils.assert_affinity_key(
+            key, self.p_af, "key", "a pool"))
+
+    def get_affinity_stats(self) -> Dict[str, Any]:
+        """Key affinity as the pool sees it: ``{"enabled", "loadFactor",
+        "claims", "hits", "spilledBusy", "spilledLoad", "queued",
+        "backends": {key: {"connections", "idle", "inUse",
+        "firstChoice", "placed"}}}``, one entry per backend the pool
+        knows.  ``claims`` counts the claims that carried a key, each
+        once: when a connection was handed to it (a hit or one of the
+        spills), or when it had to wait.  ``firstChoice`` counts the
+        ones whose first choice the backend was, ``placed`` the ones
+        that were handed one of its connections by their key.
+        ``{"enabled": False}`` when the pool was created without
+        ``claimAffinity``."""
+        af = self.p_af
+        if af is None:
+            return {"enabled": False}
+        counters = self.p_counters
+        in_use, _, _ = self._af_census()
+        out: Dict[str, Any] = {}
+        for k in self.p_keys:
+            conns = self.p_connections.get(k, ())
+            first, placed = self.p_af_placed.get(k, (0, 0))
+            out[k] = {
+                "connections": len(conns),
+                "idle": sum(1 for fsm in conns
+                            if fsm._fsm_state == "idle"),
+                "inUse": in_use.get(k, 0),
+                "firstChoice": first,
+                "placed": placed,
+            }
+        return {"enabled": True, "loadFactor": af["loadFactor"],
+                "claims": counters.get("affinity-claim", 0),
+                "hits": counters.get("affinity-hit", 0),
+                "spilledBusy": counters.get("affinity-spill-busy", 0),
+                "spilledLoad": counters.get("affinity-spill-load", 0),
+                "queued": counters.get("affinity-queued", 0),
+                "backends": out}
 
     # -- slot lifecycle ----------------------------------------------------
     def add_connection(self, key: str) -> None:
@@ -2225,6 +2577,10 @@ class ConnectionPool(FSM):
         preference: it never makes the claim wait, fail or time out.
         On a pool with ``claimQueue`` also ``priority``, the claim's
         class (an integer, 0 served first); a ValueError elsewhere.
+        On a pool with ``claimAffinity`` also ``affinityKey`` (bytes or
+        str): among the idle slots the claim prefers the backend that
+        rendezvous hashing ranks first for the key; likewise only a
+        preference, and a ValueError elsewhere.
         """
         # fast path: claim({}, cb) / claim(cb) with no CoDel — the
         # overwhelmingly common call shape on the hot path
@@ -2249,7 +2605,9 @@ class ConnectionPool(FSM):
         else:
             # (a pool whose claim() this is has no claimQueue, so a
             # ``priority`` has been refused in there)
-            cb, err_on_empty, avoid, _, timeout = \
+            # (a pool whose claim() this is has no claimAffinity
+            # either, so an ``affinityKey`` has been refused as well)
+            cb, err_on_empty, avoid, _, timeout, _ = \
                 self._claim_options(options, cb)
 
         counters = self.p_counters
@@ -2287,10 +2645,13 @@ class ConnectionPool(FSM):
     def _claim_options(self, options: Any, cb: Optional[Callable]) -> tuple:
         """Read and validate the arguments of a claim, for claim() and
         for the claim()s that opted-in pools install on themselves:
-        ``(cb, err_on_empty, avoid, priority, timeout)``.  `priority` is
-        the claim's class on a pool with ``claimQueue`` (its default
-        when the claim names none) and None on any other, where naming
-        one is an error."""
+        ``(cb, err_on_empty, avoid, priority, timeout, affinity key)``.
+        `priority` is the claim's class on a pool with ``claimQueue``
+        (its default when the claim names none) and None on any other,
+        where naming one is an error.  The affinity key is the bytes of
+        the claim's ``affinityKey`` on a pool with ``claimAffinity``,
+        None for a claim without one, and likewise an error on any
+        other pool."""
         if callable(options) and cb is None:
             cb = options
             options = {}
@@ -2306,6 +2667,9 @@ class ConnectionPool(FSM):
             prio = mod_utils.assert_claim_priority(prio, self.p_cq)
         elif self.p_cq is not None:
             prio = self.p_cq["defaultPriority"]
+        akey = options.get("affinityKey")
+        if akey is not None:
+            akey = mod_utils.assert_affinity_key(akey, self.p_af)
 
         if self.p_codel is not None:
             if options.get("timeout") is not None:
@@ -2316,16 +2680,16 @@ class ConnectionPool(FSM):
             timeout = options["timeout"]
         else:
             timeout = math.inf
-        return cb, err_on_empty, avoid, prio, timeout
+        return cb, err_on_empty, avoid, prio, timeout, akey
 
     def _claim_begin(self, options: Any, cb: Optional[Callable]) -> tuple:
         """What the claim()s of opted-in pools share: the arguments, the
         ``claim`` counter, the short-circuit of a pool that takes no
         claims, and the runtime's handle.  Returns ``(handle, stub,
-        err_on_empty, avoid, priority)``: a handle that still needs its
-        ticket and None, or None and the cancel-only stub of the
+        err_on_empty, avoid, priority, affinity key)``: a handle that
+        still needs its ticket and None, or None and the cancel-only stub of the
         short-circuit, which is then what claim() returns."""
-        cb, err_on_empty, avoid, prio, timeout = \
+        cb, err_on_empty, avoid, prio, timeout, akey = \
             self._claim_options(options, cb)
         counters = self.p_counters
         counters["claim"] = counters.get("claim", 0) + 1
@@ -2342,7 +2706,7 @@ class ConnectionPool(FSM):
             handle = ClaimHandle.fast(
                 self, mod_utils.maybe_capture_stack_trace(), cb,
                 self.p_claim_log, timeout, self._loop)
-        return handle, stub, err_on_empty, avoid, prio
+        return handle, stub, err_on_empty, avoid, prio, akey
 
     def _assert_avoid(self, avoid: Any) -> Optional[frozenset]:
         """``avoidBackends``: an iterable of backend keys.  Returns the

@@ -470,6 +470,54 @@ def assert_claim_priority(priority: Any, cq: Optional[Mapping[str, Any]],
     return priority
 
 
+_AFFINITY_KEYS = ("loadFactor",)
+
+
+def assert_claim_affinity(options: Mapping[str, Any]
+                          ) -> Optional[Dict[str, Any]]:
+    """Validate ``claimAffinity`` and return it with every default
+    filled in, or None when the option is off.  ``loadFraction`` is
+    ``loadFactor`` as an exact ratio ``(num, den)``, None for no
+    bound."""
+    from . import affinity as mod_affinity
+    af = options.get("claimAffinity")
+    if af is None:
+        return None
+    name = "options.claimAffinity"
+    if not isinstance(af, Mapping):
+        raise TypeError("%s must be a mapping" % name)
+    extra = set(af.keys()) - set(_AFFINITY_KEYS)
+    if extra:
+        raise ValueError("%s has unknown keys: %r"
+                         % (name, sorted(extra, key=str)))
+    factor = af.get("loadFactor", mod_affinity.DEFAULT_LOAD_FACTOR)
+    fraction = None
+    if factor is not None:
+        if not _num(factor):
+            raise TypeError("%s.loadFactor must be a number or None" % name)
+        if not math.isfinite(factor) or factor < 1.0:
+            raise ValueError("%s.loadFactor must be finite and >= 1.0"
+                             % name)
+        fraction = mod_affinity.load_fraction(factor)
+    return {"loadFactor": factor, "loadFraction": fraction}
+
+
+def assert_affinity_key(key: Any, af: Optional[Mapping[str, Any]],
+                        name: str = "options.affinityKey",
+                        owner: str = "a pool") -> bytes:
+    """Validate a claim's affinity key against `af`, the validated
+    ``claimAffinity`` of the pool or agent asked (None when it has
+    none), and return it as the bytes the hash reads.  Naming a key
+    where there is no ``claimAffinity`` is a ValueError."""
+    from . import affinity as mod_affinity
+    if not isinstance(key, (bytes, str)):
+        raise TypeError("%s must be bytes or str" % name)
+    if af is None:
+        raise ValueError("%s needs %s that was created with "
+                         "options.claimAffinity" % (name, owner))
+    return mod_affinity.key_bytes(key)
+
+
 RETRY_REASONS =("reset", "timeout", "status", "claim-failure")
 
 _RETRY_KEYS = ("maxRetries", "retryOn", "retryStatuses", "methods",
