@@ -87,6 +87,9 @@ class Agent(EventEmitter):
     cba_queue: Optional[Dict[str, Any]] = None
     #: the validated ``claimAffinity`` option, likewise
     cba_affinity: Optional[Dict[str, Any]] = None
+    #: the validated ``concurrencyLimit`` option, likewise: every pool
+    #: gets a copy and keeps a limit of its own
+    cba_limit: Optional[Dict[str, Any]] = None
 
     def __init__(self, options: Dict[str, Any]) -> None:
         super().__init__()
@@ -176,6 +179,10 @@ class Agent(EventEmitter):
         affinity = mod_utils.assert_claim_affinity(options)
         if affinity is not None:
             self.cba_affinity = affinity
+        # The concurrency limit (opt-in), likewise.
+        limit = mod_utils.assert_concurrency_limit(options)
+        if limit is not None:
+            self.cba_limit = limit
 
         for host in options.get("initialDomains") or ():
             self._add_pool(host, {})
@@ -290,6 +297,8 @@ class Agent(EventEmitter):
         if self.cba_affinity is not None:
             pool_opts["claimAffinity"] = {
                 "loadFactor": self.cba_affinity["loadFactor"]}
+        if self.cba_limit is not None:
+            pool_opts["concurrencyLimit"] = dict(self.cba_limit)
         if self.cba_ping is not None:
             pool_opts["checkTimeout"] = self.cba_ping_interval or 30000
             pool_opts["checker"] = \
@@ -338,6 +347,10 @@ class Agent(EventEmitter):
     def get_affinity_stats(self, host: str) -> Dict[str, Any]:
         """``ConnectionPool.get_affinity_stats()`` of `host`'s pool."""
         return self._pool_for(host).get_affinity_stats()
+
+    def get_limit_stats(self, host: str) -> Dict[str, Any]:
+        """``ConnectionPool.get_limit_stats()`` of `host`'s pool."""
+        return self._pool_for(host).get_limit_stats()
 
     def _pool_for(self, host: str) -> ConnectionPool:
         pool = self.pools.get(host)

@@ -28,6 +28,7 @@ from . import balance as mod_balance
 from . import codel as mod_codel
 from . import errors as mod_errors
 from . import latency as mod_latency
+from . import limit as mod_limit
 from . import utils as mod_utils
 from .connection_fsm import ClaimHandle, ConnectionSlotFSM
 from .events import EventEmitter
@@ -203,6 +204,10 @@ class _AffinityClaimTicket:
             handle.remove_listener("stateChanged", self)
 
 
+#: what _ticket_slow sees in place of the idle queue while the pool's
+#: concurrency limit holds claims back
+_NO_IDLE = Queue()
+
 _NativeClaimTicket = None
 _native_claim_fast = None
 _native_pool_claim = None
@@ -347,6 +352,27 @@ class ConnectionPool(FSM):
     #: placed on it]
     p_af_placed: Optional[Dict[str, List[int]]] = None
     _af_gauge = None
+
+    # Concurrency limit state, class-level like the rest: a pool without
+    # concurrencyLimit has none of these in its instance dict, its
+    # claim() is the class's and its slots keep the native dispatcher.
+    #: the validated concurrencyLimit option, defaults filled in
+    p_cl: Optional[Dict[str, Any]] = None
+    #: the limit.ConcurrencyLimiter
+    p_cl_lim: Any = None
+    #: leases in flight, and limiter.allowed() as last published
+    p_cl_inflight = 0
+    p_cl_allowed = 0
+    #: floor(limit) as the last rebalance was asked to size for
+    p_cl_floor = 0
+    #: slot -> (handle, limiter token) of a slot handed to a claim,
+    #: until the slot's 'busy' is heard
+    p_cl_handed: Optional[Dict[Any, tuple]] = None
+    #: slot -> (handle, token) of the lease seen to begin on it
+    p_cl_open: Optional[Dict[Any, tuple]] = None
+    #: slot -> last handle attributed to it (a handle has one lease)
+    p_cl_last: Optional[Dict[Any, Any]] = None
+    _cl_gauges: Optional[tuple] = None
 
     def __init__(self, options: Dict[str, Any]) -> None:
         if not callable(options.get("constructor")):
@@ -576,6 +602,36 @@ class ConnectionPool(FSM):
                 except (AttributeError, ValueError):
                     pass
 
+        # Concurrency limit (opt-in): see the "concurrency limit"
+        # section below.  Off means not one attribute is set here.  On,
+        # claim() is replaced on this instance alone, unless one of the
+        # three options above has done so: their tickets know the gate.
+        cl = mod_utils.assert_concurrency_limit(options)
+        if cl is not None:
+            self.p_cl = cl
+            self.p_cl_lim = mod_limit.ConcurrencyLimiter(cl)
+            self.p_cl_inflight = 0
+            self.p_cl_allowed = self.p_cl_lim.allowed()
+            self.p_cl_floor = int(math.floor(self.p_cl_lim.limit))
+            self.p_cl_handed = {}
+            self.p_cl_open = {}
+            self.p_cl_last = {}
+            if lb is None and cq is None and af is None:
+                self.claim = self._claim_limited
+            if self._gauge is not None:
+                try:
+                    self._cl_gauges = (
+                        self.p_collector.gauge(
+                            name="cueball_pool_concurrency_limit",
+                            help="Leases the pool may have in flight, as "
+                                 "its concurrency limit stands"),
+                        self.p_collector.gauge(
+                            name="cueball_pool_in_flight",
+                            help="Leases the pool has in flight, as its "
+                                 "concurrency limit counts them"))
+                except (AttributeError, ValueError):
+                    pass
+
         if options.get("resolver") is not None:
             self.p_resolver = options["resolver"]
             self.p_resolver_custom = True
@@ -722,6 +778,9 @@ class ConnectionPool(FSM):
             self._cq_publish()
         if self._af_gauge is not None:
             self._af_publish()
+        if self._cl_gauges is not None:
+            self._cl_gauges[0].set(self.p_cl_allowed, self._gauge_labels)
+            self._cl_gauges[1].set(self.p_cl_inflight, self._gauge_labels)
         if self.p_last_rebal_clamped:
             self.rebalance()
 
@@ -1048,6 +1107,13 @@ class ConnectionPool(FSM):
 
         if target > self.p_max:
             target = self.p_max
+        lim = self.p_cl_lim
+        if lim is not None:
+            # claims held by the limit wait for a lease to end, not for
+            # a connection: they must not open what may not be used
+            cap = int(math.floor(lim.limit)) + self.p_spares
+            if target > cap:
+                target = cap
 
         census = (target, tuple(counts), tuple(self.p_keys),
                   tuple(sorted(self.p_dead)))
@@ -1799,7 +1865,9 @@ class ConnectionPool(FSM):
         """_ticket_slow with the balancer's choice in place of the head
         of the idle queue; everything else is _ticket_slow itself."""
         if handle.is_in_state("waiting") and \
-                self._fsm_state in ("starting", "running"):
+                self._fsm_state in ("starting", "running") and not (
+                    self.p_cl_lim is not None and
+                    self.p_cl_inflight >= self.p_cl_allowed):
             picked = self._lb_pick(avoid)
             if picked is not None:
                 fsm, reordered = picked
@@ -1815,6 +1883,8 @@ class ConnectionPool(FSM):
                 else:
                     self.p_lb_handed[fsm] = (handle, rec)
                     rec.picked += 1
+                    if self.p_cl_lim is not None:
+                        self._cl_handoff(handle, fsm)
                     counters = self.p_counters
                     counters["balanced-claim"] = \
                         counters.get("balanced-claim", 0) + 1
@@ -1823,8 +1893,8 @@ class ConnectionPool(FSM):
                             counters.get("balanced-reordered", 0) + 1
                 self._note_demand()
                 return
-        # nothing idle (the walk has emptied the queue), or the pool is
-        # on its way out
+        # nothing idle (the walk has emptied the queue), the pool is on
+        # its way out, or it is at its concurrency limit
         self._ticket_slow(handle, err_on_empty)
 
     def _claim_balanced(self, options: Any = None,
@@ -2198,7 +2268,9 @@ class ConnectionPool(FSM):
         the idle queue; everything else is _ticket_slow itself."""
         order: List[str] = []
         if handle.is_in_state("waiting") and \
-                self._fsm_state in ("starting", "running"):
+                self._fsm_state in ("starting", "running") and not (
+                    self.p_cl_lim is not None and
+                    self.p_cl_inflight >= self.p_cl_allowed):
             order = self._af_order(ticket.key)
             avoid = ticket.avoid
             if avoid is not None:
@@ -2223,6 +2295,8 @@ class ConnectionPool(FSM):
                 else:
                     if rec is not None:
                         self.p_lb_handed[fsm] = (handle, rec)
+                    if self.p_cl_lim is not None:
+                        self._cl_handoff(handle, fsm)
                     if not ticket.counted:
                         first = order[0] if order else None
                         if key == first:
@@ -2234,8 +2308,8 @@ class ConnectionPool(FSM):
                         self._af_count(ticket, outcome, first, key)
                 self._note_demand()
                 return
-        # nothing idle (the walk has emptied the queue), or the pool is
-        # on its way out
+        # nothing idle (the walk has emptied the queue), the pool is on
+        # its way out, or it is at its concurrency limit
         self._ticket_slow(handle, ticket.err_on_empty)
         if not ticket.counted and handle._fsm_state == "waiting":
             self._af_count(ticket, "affinity-queued",
@@ -2250,6 +2324,8 @@ class ConnectionPool(FSM):
         and an _AffinityClaimTicket."""
         if not isinstance(options, Mapping) or \
                 options.get("affinityKey") is None:
+            if self.p_cl_lim is not None:
+                return self._claim_limited(options, cb)
             return ConnectionPool.claim(self, options, cb)
         handle, stub, err_on_empty, avoid, _, akey = \
             self._claim_begin(options, cb)
@@ -2312,6 +2388,187 @@ class ConnectionPool(FSM):
                 "queued": counters.get("affinity-queued", 0),
                 "backends": out}
 
+    # -- concurrency limit (opt-in) ------------------------------------------
+    #
+    # With ``concurrencyLimit`` the pool carries at most ``allowed()``
+    # leases at once, a number that follows measured lease latency
+    # (cueball_amd.limit).  ``maximum`` stays what it is, a bound on
+    # sockets; the limit bounds the work in flight.
+    #
+    # The gate sits wherever an idle slot meets a claim.  A claim's
+    # ticket that finds the pool at its limit takes no idle slot and
+    # queues as if none were idle (the ticket gate); a slot that goes
+    # idle while the pool is at its limit parks on the idle queue and
+    # leaves the waiters where they are (the feed gate); and whenever
+    # room appears, by the limit rising or a lease ending, head waiters
+    # are fed from the head of the idle queue (the kick).
+    #
+    # Leases are observed from outside the claim path, by the scheme of
+    # claim balancing above.  A lease counts from the try_ that hands
+    # its slot over, so that a burst of claims in one loop turn sees
+    # itself, and until the slot's next state after 'busy' is heard, or
+    # the 'busy' that is heard shows that nothing came of the try.  It
+    # is timed on the loop's clock between the two.  A lease that failed
+    # leaves no sample; pinger leases are never seen.
+    #
+    # Accounting and gate share one stateChanged listener per slot,
+    # installed in place of the native dispatcher: the lease's end is
+    # counted, then _slot_state_changed sees the slot, then the kick.
+
+    def _cl_held(self) -> bool:
+        """Is the pool at its limit?  Asked by a ticket about to take an
+        idle slot; ``limit-held`` counts the times one was there."""
+        if self.p_cl_inflight < self.p_cl_allowed:
+            return False
+        for fsm in self.p_idleq:
+            if fsm._fsm_state == "idle":
+                self._incr_counter("limit-held")
+                break
+        return True
+
+    def _cl_handoff(self, handle: ClaimHandle,
+                    fsm: ConnectionSlotFSM) -> None:
+        """After every ``handle.try_(fsm)`` of an opted-in pool."""
+        if handle._fsm_state in ("waiting", "cancelled"):
+            return      # rejected: the slot's socket was gone already
+        self.p_cl_handed[fsm] = (
+            handle, self.p_cl_lim.on_start(self._loop.time() * 1000.0))
+        self.p_cl_inflight += 1
+
+    def _cl_slot_changed(self, fsm: ConnectionSlotFSM, key: str,
+                         st: str) -> None:
+        fell = False
+        if st == "busy":
+            handed = self.p_cl_handed.pop(fsm, None)
+            hdl = fsm.csf_handle
+            if hdl is None:
+                hdl = fsm.csf_prev_handle
+            # a claim the slot rejected leaves no handle behind, and
+            # csf_prev_handle is then the lease before: seen already
+            if hdl is None or hdl is self.p_cl_last.get(fsm) or \
+                    hdl.ch_slot is not fsm or hdl._fsm_state not in (
+                        "claimed", "released", "closed"):
+                hdl = None
+            if handed is not None and handed[0] is not hdl:
+                self._cl_ended(handed[1], None)     # nothing came of it
+                fell = True
+                handed = None
+            if hdl is not None:
+                self.p_cl_last[fsm] = hdl
+                if not hdl.ch_pinger:
+                    if handed is None:
+                        # handed over by something that does not report
+                        # to _cl_handoff: counted from here
+                        handed = (hdl, self.p_cl_lim.on_start(
+                            self._loop.time() * 1000.0))
+                        self.p_cl_inflight += 1
+                    self.p_cl_open[fsm] = handed
+        else:
+            ent = self.p_cl_open.pop(fsm, None)
+            if ent is not None:
+                hdl, token = ent
+                if hdl._fsm_state == "closed" or hdl.ch_failure_reported \
+                        or st in ("retrying", "connecting", "failed",
+                                  "stopped"):
+                    self._cl_ended(token, None)
+                else:
+                    now = self._loop.time() * 1000.0
+                    self._cl_ended(token, now - token[0])
+                fell = True
+            if st == "stopped" or st == "failed":
+                self.p_cl_last.pop(fsm, None)
+                handed = self.p_cl_handed.pop(fsm, None)
+                if handed is not None:
+                    self._cl_ended(handed[1], None)
+                    fell = True
+        self._slot_state_changed(fsm, key, st)
+        if fell:
+            self._cl_kick()
+
+    def _cl_ended(self, token: tuple, hold_ms: Optional[float]) -> None:
+        """One lease less in flight; with `hold_ms` None it leaves no
+        sample."""
+        self.p_cl_inflight -= 1
+        lim = self.p_cl_lim
+        if hold_ms is None:
+            lim.on_discard(token)
+            return
+        was_probing = lim.probing
+        lim.on_sample(token, hold_ms, self._loop.time() * 1000.0)
+        if lim.probing and not was_probing:
+            self._incr_counter("limit-probe")
+        floor = int(math.floor(lim.limit))
+        if floor != self.p_cl_floor:
+            self._incr_counter("limit-raised" if floor > self.p_cl_floor
+                               else "limit-lowered")
+            self.p_cl_floor = floor
+            self.rebalance()
+        allowed = lim.allowed()
+        previous = self.p_cl_allowed
+        if allowed != previous:
+            # the limit moved, or a probe began or ended
+            self.p_cl_allowed = allowed
+            self.emit("limitChanged", allowed, previous)
+
+    def _cl_kick(self) -> None:
+        """Room has appeared under the limit: feed head waiters from the
+        head of the idle queue until waiters, idle slots or room run
+        out."""
+        if self._fsm_state not in ("starting", "running"):
+            return
+        idleq = self.p_idleq
+        waiters = self.p_waiters
+        while waiters._len > 0 and idleq._len > 0 and \
+                self.p_cl_inflight < self.p_cl_allowed:
+            fsm = idleq.shift()
+            fsm.p_idleq_node = None
+            if not fsm.is_in_state("idle"):
+                continue
+            if not self._feed_waiters(fsm):
+                # every waiter had gone: back where the slot came from
+                fsm.p_idleq_node = idleq.unshift(fsm)
+                break
+
+    def _claim_limited(self, options: Any = None,
+                       cb: Optional[Callable] = None):
+        """claim() of a pool with ``concurrencyLimit`` and none of
+        ``claimBalancing``, ``claimQueue`` and ``claimAffinity``
+        (installed on the instance): the same options, counters and
+        return values.  The handle is the runtime's own; its ticket is a
+        Python one on either runtime, so that every try passes the gate
+        in _ticket_slow."""
+        handle, stub, err_on_empty, avoid, _, _ = \
+            self._claim_begin(options, cb)
+        if handle is None:
+            return stub
+        handle.on("stateChanged",
+                  _AvoidClaimTicket(self, handle, err_on_empty, avoid))
+        return handle
+
+    def get_limit_stats(self) -> Dict[str, Any]:
+        """The concurrency limit as the pool sees it: ``{"enabled",
+        "algorithm", "limit", "allowed", "inFlight", "probing",
+        "baselineMs", "lastWindowMeanMs", "windows", "probes",
+        "samples", "discarded", "raised", "lowered"}``.  ``limit`` is
+        the controller's float, ``allowed`` the integer in force (the
+        probe's while ``probing``); ``baselineMs`` is None under
+        ``"aimd"`` and before the first probe has ended;
+        ``discarded`` counts the leases that left no sample, ``raised``
+        and ``lowered`` the windows that moved the limit.
+        ``{"enabled": False}`` when the pool was created without
+        ``concurrencyLimit``."""
+        lim = self.p_cl_lim
+        if lim is None:
+            return {"enabled": False}
+        return {"enabled": True, "algorithm": lim.algorithm,
+                "limit": lim.limit, "allowed": self.p_cl_allowed,
+                "inFlight": self.p_cl_inflight, "probing": lim.probing,
+                "baselineMs": lim.baseline,
+                "lastWindowMeanMs": lim.last_mean,
+                "windows": lim.windows, "probes": lim.probes,
+                "samples": lim.samples, "discarded": lim.discarded,
+                "raised": lim.raised, "lowered": lim.lowered}
+
     # -- slot lifecycle ----------------------------------------------------
     def add_connection(self, key: str) -> None:
         if self.is_in_state("stopping") or self.is_in_state("stopped"):
@@ -2340,7 +2597,12 @@ class ConnectionPool(FSM):
         # Native dispatcher when available (idle-feed/busy fast paths
         # in C, everything else falls back to _slot_state_changed);
         # else functools.partial, which dispatches at C level.
-        if _NativeSlotDispatch is not None:
+        if self.p_cl_lim is not None:
+            # the limit's accounting and its gate in one listener, in
+            # this order whatever else is registered (see _cl_slot_changed)
+            fsm.on("stateChanged",
+                   functools.partial(self._cl_slot_changed, fsm, key))
+        elif _NativeSlotDispatch is not None:
             fsm.on("stateChanged", _NativeSlotDispatch(
                 self, fsm, key, self.p_codel is not None))
         else:
@@ -2376,21 +2638,14 @@ class ConnectionPool(FSM):
                     fsm.set_unwanted()
                     return
 
-                # Feed waiters, with the CoDel drop check on each.
-                while self.p_waiters._len > 0:
-                    hdl = self.p_waiters.shift()
-                    drop = self.p_codel is not None and \
-                        self.p_codel.overloaded(hdl.ch_started)
-                    if not hdl.is_in_state("waiting"):
-                        continue
-                    if drop:
-                        hdl.timeout()
-                        continue
-                    hdl.try_(fsm)
+                if self.p_cl_lim is not None and \
+                        self.p_waiters._len > 0 and \
+                        self.p_cl_inflight >= self.p_cl_allowed:
+                    # the feed gate: at the limit the waiters stay, and
+                    # the slot parks until _cl_kick comes for it
+                    pass
+                elif self._feed_waiters(fsm):
                     return
-
-                if self.p_codel is not None:
-                    self.p_codel.empty()
 
                 fsm.p_idleq_node = self.p_idleq.push(fsm)
                 return
@@ -2433,6 +2688,29 @@ class ConnectionPool(FSM):
             fsm.p_idleq_node = None
             self.rebalance()
 
+    def _feed_waiters(self, fsm: ConnectionSlotFSM) -> bool:
+        """Offer the idle `fsm` to the head waiter, with the CoDel drop
+        check on each dequeue; False when no waiter was left to take it
+        (the queue is empty then, and CoDel is told so)."""
+        waiters = self.p_waiters
+        while waiters._len > 0:
+            hdl = waiters.shift()
+            drop = self.p_codel is not None and \
+                self.p_codel.overloaded(hdl.ch_started)
+            if not hdl.is_in_state("waiting"):
+                continue
+            if drop:
+                hdl.timeout()
+                continue
+            hdl.try_(fsm)
+            if self.p_cl_lim is not None:
+                self._cl_handoff(hdl, fsm)
+            return True
+
+        if self.p_codel is not None:
+            self.p_codel.empty()
+        return False
+
     def print_connections(self) -> None:
         """Debugging helper: dump live connection states and dead set
         (lib/pool.js:812-832)."""
@@ -2471,6 +2749,9 @@ class ConnectionPool(FSM):
         avoid = None
         if avoidBackends is not None:
             avoid = self._assert_avoid(avoidBackends)
+        if self.p_cl_lim is not None and \
+                self.p_cl_inflight >= self.p_cl_allowed:
+            return False    # idle, but not to be had: see _cl_held
         for fsm in self.p_idleq:
             if fsm.is_in_state("idle") and (
                     avoid is None or
@@ -2528,12 +2809,18 @@ class ConnectionPool(FSM):
         # stale ('stateChanged' is async): just unlink and skip them;
         # the slot dispatcher copes (lib/pool.js:934-951).
         idleq = self.p_idleq
-        if avoid is not None:
+        lim = self.p_cl_lim
+        if lim is not None and self._cl_held():
+            # at the concurrency limit: queued as if nothing were idle
+            idleq = _NO_IDLE
+        elif avoid is not None:
             # a soft preference among the idle slots, nothing more:
             # from here on the claim is like any other
             fsm = self._idle_avoiding(avoid)
             if fsm is not None:
                 handle.try_(fsm)
+                if lim is not None:
+                    self._cl_handoff(handle, fsm)
                 self._note_demand()
                 return
         while idleq._len > 0:
@@ -2542,6 +2829,8 @@ class ConnectionPool(FSM):
             if not fsm.is_in_state("idle"):
                 continue
             handle.try_(fsm)
+            if lim is not None:
+                self._cl_handoff(handle, fsm)
             self._note_demand()
             return
 

@@ -518,6 +518,128 @@ def assert_affinity_key(key: Any, af: Optional[Mapping[str, Any]],
     return mod_affinity.key_bytes(key)
 
 
+_LIMIT_COMMON_KEYS = ("algorithm", "window", "minSamples", "minLimit",
+                      "maxLimit", "initialLimit")
+_LIMIT_KEYS = {
+    "aimd": _LIMIT_COMMON_KEYS + ("latencyThreshold", "backoffRatio"),
+    "gradient": _LIMIT_COMMON_KEYS + (
+        "tolerance", "smoothing", "probeInterval", "probeSpread",
+        "probeLimit", "probeSamples", "random"),
+}
+
+
+def assert_concurrency_limit(options: Mapping[str, Any]
+                             ) -> Optional[Dict[str, Any]]:
+    """Validate ``concurrencyLimit`` against the pool's ``maximum`` and
+    return it with every default filled in (``random`` None meaning the
+    ``random`` module), or None when the option is off (None or False).
+    True stands for ``{}``: every default, which is the gradient
+    controller."""
+    cl = options.get("concurrencyLimit")
+    if cl is None or cl is False:
+        return None
+    name = "options.concurrencyLimit"
+    if cl is True:
+        cl = {}
+    if not isinstance(cl, Mapping):
+        raise TypeError("%s must be a mapping or a bool" % name)
+    algorithm = cl.get("algorithm")
+    if algorithm is None:
+        algorithm = "gradient"
+    if not isinstance(algorithm, str):
+        raise TypeError("%s.algorithm must be a string" % name)
+    if algorithm not in _LIMIT_KEYS:
+        raise ValueError("%s.algorithm must be one of %r"
+                         % (name, sorted(_LIMIT_KEYS)))
+    extra = set(cl.keys()) - set(_LIMIT_KEYS[algorithm])
+    if extra:
+        raise ValueError("%s has unknown keys under %r: %r"
+                         % (name, algorithm, sorted(extra, key=str)))
+
+    def number(key: str, default: Any) -> Any:
+        v = cl.get(key)
+        if v is None:
+            return default
+        if not _num(v):
+            raise TypeError("%s.%s must be a number" % (name, key))
+        if not math.isfinite(v):
+            raise ValueError("%s.%s must be finite" % (name, key))
+        return v
+
+    def integer(key: str, default: Any) -> Any:
+        v = cl.get(key)
+        if v is None:
+            return default
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise TypeError("%s.%s must be an int" % (name, key))
+        return v
+
+    maximum = options.get("maximum")
+    window = number("window", 1000)
+    if window <= 0:
+        raise ValueError("%s.window must be > 0" % name)
+    min_samples = integer("minSamples", 10)
+    if min_samples < 1:
+        raise ValueError("%s.minSamples must be >= 1" % name)
+    min_limit = integer("minLimit", 1)
+    max_limit = integer("maxLimit", maximum)
+    if not isinstance(max_limit, int) or isinstance(max_limit, bool):
+        raise TypeError("%s.maxLimit needs the pool's maximum" % name)
+    if min_limit < 1:
+        raise ValueError("%s.minLimit must be >= 1" % name)
+    if not (min_limit <= max_limit) or \
+            (isinstance(maximum, int) and max_limit > maximum):
+        raise ValueError("%s needs minLimit <= maxLimit <= maximum" % name)
+    initial = number("initialLimit", max_limit)
+    if not (min_limit <= initial <= max_limit):
+        raise ValueError("%s.initialLimit must be in minLimit..maxLimit"
+                         % name)
+    out: Dict[str, Any] = {
+        "algorithm": algorithm, "window": window,
+        "minSamples": min_samples, "minLimit": min_limit,
+        "maxLimit": max_limit, "initialLimit": initial}
+
+    if algorithm == "aimd":
+        threshold = number("latencyThreshold", None)
+        if threshold is None:
+            raise ValueError('%s.latencyThreshold is required under '
+                             'algorithm "aimd"' % name)
+        if threshold <= 0:
+            raise ValueError("%s.latencyThreshold must be > 0" % name)
+        ratio = number("backoffRatio", 0.9)
+        if not (0.5 <= ratio < 1):
+            raise ValueError("%s.backoffRatio must be in [0.5, 1)" % name)
+        out.update(latencyThreshold=threshold, backoffRatio=ratio)
+        return out
+
+    tolerance = number("tolerance", 1.5)
+    if tolerance < 1.0:
+        raise ValueError("%s.tolerance must be >= 1.0" % name)
+    smoothing = number("smoothing", 0.2)
+    if not (0 < smoothing <= 1):
+        raise ValueError("%s.smoothing must be in (0, 1]" % name)
+    interval = number("probeInterval", 30000)
+    if interval <= 0:
+        raise ValueError("%s.probeInterval must be > 0" % name)
+    spread = number("probeSpread", 0.15)
+    if not (0 <= spread < 1):
+        raise ValueError("%s.probeSpread must be in [0, 1)" % name)
+    probe_limit = integer("probeLimit", 3)
+    if probe_limit < 1:
+        raise ValueError("%s.probeLimit must be >= 1" % name)
+    probe_samples = integer("probeSamples", min_samples)
+    if probe_samples < 1:
+        raise ValueError("%s.probeSamples must be >= 1" % name)
+    rnd = cl.get("random")
+    if rnd is not None and not callable(getattr(rnd, "random", None)):
+        raise TypeError("%s.random must have a random() method" % name)
+    out.update(tolerance=tolerance, smoothing=smoothing,
+               probeInterval=interval, probeSpread=spread,
+               probeLimit=probe_limit, probeSamples=probe_samples,
+               random=rnd)
+    return out
+
+
 RETRY_REASONS =("reset", "timeout", "status", "claim-failure")
 
 _RETRY_KEYS = ("maxRetries", "retryOn", "retryStatuses", "methods",
